@@ -4,8 +4,9 @@
 One "step" = one reverse-diffusion step over the per-GPU batch: a full UNet forward on the HIP
 engine + the fused scheduler update (reference sample_ddpm.py:37-44).  The timed region runs
 EXACTLY --steps consecutive steps of the T=1000 schedule starting at t=999 (default 1000 = one
-complete sample, x_T -> x_0, including the final all-gather of x_0 when N>1); images/s =
-(images in flight) * (steps / T) / elapsed, so a full run is the literal job throughput.
+complete sample, x_T -> x_0, including the final all-gather of x_0 when N>1; past T the schedule
+starts over at t=999); images/s = (images in flight) * (steps / T) / elapsed, so a full run is the
+literal job throughput.
 
 Workload (BASELINE config 2 at N=1, config 5 at N=8): S=256, 16 images per GPU (weak scaling),
 fp32, the default config.yaml UNet (110.08 M params) with keyed synthetic weights, Philox device
@@ -14,7 +15,11 @@ noise keyed by (seed, global sample, step).
 Launch: python bench.py [--gpus N --steps K --warmup W].  N>1: under torch.distributed.run (RCCL,
 WORLD_SIZE must equal --gpus); without WORLD_SIZE in the environment bench.py starts
 ``torch.distributed.run --nproc-per-node N`` itself as a child process (before any GPU call) and exits
-with its code.  Rank 0 prints ONE JSON line.  Extra legs (rank 0, after the timed region):
+with its code.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and
+prints the line (ms_per_step = the milliseconds one timed step took); --dump-outputs DIR also writes
+the last timed step's eps and x (float32, DIR/eps.npy, DIR/x.npy; the inputs are the same from run to
+run: keyed weights, Philox noise keyed by --seed).  Extra legs, only with --full (rank 0, after the
+timed region):
   roofline      per-launch HIP events around every conv of one UNet forward; the dominant kernel
                 is the conv instantiation with the most time (the GN+SiLU-prologue 3x3 convs) —
                 achieved = its algorithmic (fp32-equivalent) FLOPs per launch / its mean launch
@@ -68,6 +73,11 @@ def parse(argv=None):
     ap.add_argument('--vp-wide', type=int, default=0,
                     help='eager runs (--graph 0): the pre-split convs in the form the two-group graph uses '
                          '(kernels.wino_vp_wide), so a PMC pass at --batch B/2 sees the timed instantiations')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run the extra legs (roofline, parity, cpu_baseline); a plain '
+                         'run only sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (eps, x) as DIR/<name>.npy in float32')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-batch', type=int, default=None, help='CPU baseline batch (default: --batch)')
@@ -82,7 +92,36 @@ def parse(argv=None):
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='process-group backend for N>1: nccl (= RCCL over xGMI, the benched path) or gloo '
                          '(x0 gather staged through host memory; lets N ranks share one GPU for rehearsal)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all arrays of one run together stay under this
+
+
+def dump_outputs(path: str, arrays: dict, seed: int, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Write every tensor of `arrays` as <path>/<name>.npy in float32 (float64 stays float64).  The
+    budget is shared equally; an array over its share is stored as a fixed sample of its flattened
+    elements (indices drawn without replacement by numpy's default_rng(seed), sorted), so two runs with
+    the same arguments store the same elements.  Returns {name: {'shape', 'stored', 'sampled'}}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    info = {}
+    for name, ten in arrays.items():
+        a = ten.detach().cpu()
+        a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        sampled = a.nbytes > share
+        if sampled:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=share // a.itemsize, replace=False))
+            out = a.reshape(-1)[idx]
+        else:
+            out = a
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(out))
+        info[name] = {'shape': list(a.shape), 'stored': int(out.size), 'sampled': bool(sampled)}
+    return info
 
 
 KERNEL_DESC = {
@@ -591,7 +630,7 @@ def main():
     sched = LinearNoiseScheduler(args.timesteps, 0.0001, 0.02, device=dev)
     B = args.batch
     T = args.timesteps
-    K = min(args.steps, T)
+    K = args.steps  # past T the schedule starts over at t = T - 1 (same cost per step)
     sample0 = rank * B
     shape = (B, mc.im_channels, mc.im_size, mc.im_size)
     ts = torch.arange(T, device=dev, dtype=torch.long)
@@ -625,7 +664,8 @@ def main():
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for i in range(T - 1, T - 1 - K, -1):
+        for j in range(K):
+            i = T - 1 - (j % T)
             eps = fwd(x, ts[i:i + 1])
             if i == 0:
                 sched.step(x, eps, 0, out=nxt)
@@ -651,6 +691,15 @@ def main():
         finite = bool(torch.isfinite(x).all())
         if gathered is not None:
             finite = finite and bool(torch.isfinite(gathered).all())
+
+        dumped = None
+        if rank == 0 and args.dump_outputs:
+            # what a caller of the timed step receives from its last step: the UNet's eps and the
+            # scheduler's x_{t-1} (rank 0's block; with a process group also the gathered batch)
+            arrays = {'eps': eps, 'x': x}
+            if gathered is not None:
+                arrays['x_gathered'] = gathered
+            dumped = dump_outputs(args.dump_outputs, arrays, args.seed)
 
         result = None
         if rank == 0:
@@ -704,16 +753,18 @@ def main():
                 'gathered_shape': list(gathered.shape) if gathered is not None else None,
                 'unet_step_tflops_algorithmic': round(unet_tflops, 2) if unet_tflops else None,
             }
-            if not args.no_roofline:
+            if dumped is not None:
+                result['outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
+            if args.full and not args.no_roofline:
                 # the dominant kernel as the timed graph launches it: one image group
                 g = runner.split if runner is not None else 1
                 from weatherconverter_amd.kernels import wino_vp_wide
                 with wino_vp_wide(g > 1):  # the same instantiations as the timed graph (its groups' form)
                     result['roofline'] = roofline_leg(model, x[:B // g], ts[500:501], groups=g)
-            if not args.no_parity and args.size == 256:
+            if args.full and not args.no_parity and args.size == 256:
                 result['parity'] = parity_leg(model, dev)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline_leg(args)
         else:
             result['cpu_baseline'] = None

@@ -86,6 +86,42 @@ def test_self_launch_refused_under_profiler(monkeypatch):
         bench._self_launch(bench.parse(['--gpus', '2']))
 
 
+def test_plain_run_is_the_default_and_steps_are_taken_literally():
+    """--full (the roofline / parity / cpu_baseline legs) and --dump-outputs are off by default; --steps is
+    not capped by the schedule length and must be positive."""
+    args = bench.parse(['--gpus', '1', '--steps', '1500', '--warmup', '2'])
+    assert args.full is False and args.dump_outputs is None
+    assert args.steps == 1500 and args.timesteps == 1000
+    assert bench.parse(['--full', '--dump-outputs', 'd']).full is True
+    with pytest.raises(SystemExit):
+        bench.parse(['--steps', '0'])
+
+
+def test_dump_outputs_float32_npy_and_seeded_sample_over_budget(tmp_path):
+    """dump_outputs stores float32 arrays whole while they fit their share of the budget, a larger one as
+    the same seeded sample of its elements on every call, and never more than the budget in all."""
+    import numpy as np
+    import torch
+    big = torch.arange(3000, dtype=torch.float32).reshape(3, 10, 100)
+    small = torch.arange(8, dtype=torch.float64).reshape(2, 4)
+    info = bench.dump_outputs(str(tmp_path / 'a'), {'big': big, 'small': small}, seed=7, budget=8000)
+    again = bench.dump_outputs(str(tmp_path / 'b'), {'big': big, 'small': small}, seed=7, budget=8000)
+    assert info == again
+    assert info['small'] == {'shape': [2, 4], 'stored': 8, 'sampled': False}
+    assert info['big'] == {'shape': [3, 10, 100], 'stored': 1000, 'sampled': True}
+    s = np.load(tmp_path / 'a' / 'small.npy')
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())
+    b = np.load(tmp_path / 'a' / 'big.npy')
+    assert b.dtype == np.float32 and b.shape == (1000, )
+    assert np.all(np.diff(b) > 0) and b.min() >= 0 and b.max() < 3000  # distinct elements of the array, in order
+    assert np.array_equal(b, np.load(tmp_path / 'b' / 'big.npy'))
+    assert b.nbytes + s.nbytes <= 8000
+    half = torch.ones(4, 4, dtype=torch.float16)
+    bench.dump_outputs(str(tmp_path / 'c'), {'h': half}, seed=7)
+    h = np.load(tmp_path / 'c' / 'h.npy')
+    assert h.dtype == np.float32 and h.shape == (4, 4)
+
+
 def test_hbm_leg_bytes_from_nbytes_or_flops_field():
     """hbm_leg reads a launch's stated nbytes (wino_vsplit) and falls back to the 'flops' field, where the
     GroupNorm / split wrappers state their bytes."""
