@@ -607,32 +607,33 @@ def _check(ours, ref, per_tensor=1e-4, overall=1e-5):
 
 
 @pytest.mark.parametrize('precision', ['f16x3', 'bf16x6', 'fp32'])
-def test_unet_grads_tiny_vs_oracle_autograd(precision, monkeypatch):
-    # f16x3: every tracked gradient range bound is checked against a fresh absmax of its tensor
-    monkeypatch.setenv('WC_CHECK_GBOUND', '1')
+def test_unet_grads_tiny_vs_oracle_autograd(precision):
     import json
     import os
     from conftest import GOLDEN
+    from weatherconverter_amd import forms
     from weatherconverter_amd.diffusion_model.config import ModelConfig
     man = json.load(open(os.path.join(GOLDEN, 'manifest.json')))
     mc = ModelConfig(**man['tiny']['config'])
-    ours, ref, lo, lr = _model_grads(mc, 3, precision)
+    # f16x3: every tracked gradient range bound is checked against a fresh absmax of its tensor
+    with forms.using(check_gbound=True):
+        ours, ref, lo, lr = _model_grads(mc, 3, precision)
     assert abs(lo - lr) <= 1e-5 * abs(lr)
     _check(ours, ref)
 
 
 @pytest.mark.parametrize('line', ['f16', 'bf16'])
-def test_unet_grads_16bit_training_lines_vs_oracle_autograd(line, monkeypatch):
+def test_unet_grads_16bit_training_lines_vs_oracle_autograd(line):
     """The 16-bit training lines (train precision 'f16': the single-piece build, one fp16 piece per
     operand; 'bf16': one bf16 piece per operand on the bf16 MFMA, BASELINE config 3's arithmetic; fp32
     accumulation) on the 256-px architecture at B=2: their gradient error against float64 autograd is
     that of 16-bit operands — bounded here at 2e-2 (f16) / 6e-2 (bf16) overall and 1e-1 / 3e-1 per
     tensor (the fp32-class modes: 1e-5 / 1e-4) — and the single-piece kernels actually ran (their error
     is far above f16x3's)."""
-    monkeypatch.setenv('WC_CHECK_GBOUND', '1')
-    from weatherconverter_amd import _native
+    from weatherconverter_amd import _native, forms
     from weatherconverter_amd.diffusion_model.config import model_config
-    ours, ref, lo, lr = _model_grads(model_config(256), 2, line)
+    with forms.using(check_gbound=True):
+        ours, ref, lo, lr = _model_grads(model_config(256), 2, line)
     assert {'f16': 'single16', 'bf16': 'bf16'}[line] in _native._libs
     a = torch.cat([ours[k].flatten() for k in ref])
     b = torch.cat([ref[k].flatten() for k in ref])
@@ -644,10 +645,11 @@ def test_unet_grads_16bit_training_lines_vs_oracle_autograd(line, monkeypatch):
     _check(ours, ref, per_tensor=1e-1 if line == 'f16' else 3e-1, overall=overall)
 
 
-def test_unet_grads_256_baseline_architecture_vs_oracle_autograd(monkeypatch):
-    monkeypatch.setenv('WC_CHECK_GBOUND', '1')
+def test_unet_grads_256_baseline_architecture_vs_oracle_autograd():
+    from weatherconverter_amd import forms
     from weatherconverter_amd.diffusion_model.config import model_config
-    ours, ref, lo, lr = _model_grads(model_config(256), 2, 'f16x3')
+    with forms.using(check_gbound=True):
+        ours, ref, lo, lr = _model_grads(model_config(256), 2, 'f16x3')
     assert len(ref) == 358
     assert abs(lo - lr) <= 1e-5 * abs(lr)
     _check(ours, ref)

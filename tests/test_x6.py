@@ -596,11 +596,12 @@ def test_igemm_f16x3_pointwise_vector_epilogue(sw, pa):
 
 
 @pytest.mark.gpu
-def test_projections_presplit_bit_identical_to_register_staged(monkeypatch):
+def test_projections_presplit_bit_identical_to_register_staged():
     """The attention projections on a pre-split A operand (GN applied and split once by
     wc_split_f16x3_tiled, both operands copied by LDS-DMA) compute the same split values in the
     same MFMA order as the register-staged implicit GEMM: the UNet forward (256-cfg at 64 px, B=2,
     per-sample t) is bit-identical with WC_PROJ_PA=1 and 0; and the pre-split q/k/v equal too."""
+    from weatherconverter_amd import forms
     from weatherconverter_amd import kernels as K
     from weatherconverter_amd.diffusion_model.config import model_config
     from weatherconverter_amd.diffusion_model.models.unet_base import Unet
@@ -613,8 +614,7 @@ def test_projections_presplit_bit_identical_to_register_staged(monkeypatch):
     x = torch.randn((2, 3, 64, 64), generator=torch.Generator().manual_seed(9)).cuda()
     outs = []
     for pa in ('1', '0'):
-        monkeypatch.setenv('WC_PROJ_PA', pa)
-        with torch.no_grad():
+        with forms.using(proj_pa=(pa == '1')), torch.no_grad():
             outs.append(net(x, torch.tensor([700, 3]).cuda()).cpu())
     assert torch.equal(outs[0], outs[1])
     # the qkv projection alone: GN prologue in the kernel vs GN in the split pass

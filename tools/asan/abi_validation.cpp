@@ -11,6 +11,10 @@
 
 #include "wc_kernels.h"
 
+// The library build generates this symbol (the digest of its sources, _build.py); the harness links the
+// objects directly, so it supplies its own for wc_version to refer to.
+extern "C" const char* wc_source_hash(void) { return "asan-harness"; }
+
 static int failures = 0;
 
 #define EXPECT(expr, want)                                                                       \
@@ -108,10 +112,9 @@ int main() {
     EXPECT(wc_pack_split(p, 144, 4, 16, 9, 0, 0, 0, 0, 100, p, 0, p, nullptr), WC_E_ARG);  // BN not 64 / 128
 
     // Kernel-form selectors: out-of-range modes rejected, valid ones return the previous setting.
-    EXPECT(wc_conv3x3_set_onewave(2), WC_E_ARG);
     EXPECT(wc_proj_set_tile(64), WC_E_ARG);
-    if (wc_conv3x3_set_onewave(1) != 0 || wc_conv3x3_set_onewave(0) != 1 || wc_proj_set_tile(256) != 0 ||
-        wc_proj_set_tile(-128) != 256 || wc_proj_set_tile(128) != -128 || wc_proj_set_tile(0) != 128) {
+    EXPECT(wc_proj_set_tile(-128), WC_E_ARG);
+    if (wc_proj_set_tile(256) != 0 || wc_proj_set_tile(128) != 256 || wc_proj_set_tile(0) != 128) {
         std::printf("FAIL kernel-form selectors\n");
         ++failures;
     }

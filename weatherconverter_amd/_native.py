@@ -11,7 +11,7 @@ import threading
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-from . import _build
+from . import _build, forms
 
 MAX_TAPS = 16
 NOISE_NONE, NOISE_TENSOR, NOISE_PHILOX = 0, 1, 2
@@ -213,6 +213,7 @@ def load(build_if_missing: bool = True):
         _build.build()
     lib = ctypes.CDLL(path)
     verify_source_hash(lib, v)
+    forms.announce()  # a run with non-default kernel forms says so before its first native call
     stale_ok = os.environ.get('WC_ALLOW_STALE_LIB', '0') == '1'
     for name, argtypes in _SIGS.items():
         if stale_ok and not hasattr(lib, name):  # an older A/B build may lack newer entry points

@@ -45,12 +45,12 @@ Per attention layer (``unet_base.py:153-161``), in place on Y::
 Modes ``bf16x6`` / ``fp32`` (``set_conv_precision``) run the same structure on the direct halo
 kernels (``wc_conv3x3_x6``) and implicit-GEMM convs (``wc_conv_igemm``).
 """
-import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import torch
 
+from ... import forms
 from ... import kernels as K
 from ...kernels import Seg, View
 
@@ -96,7 +96,7 @@ class ResPack:
     w2f3: Optional[K.X6Weight] = None
     gb1: Tuple[float, float] = (0.0, 0.0)  # (max|gamma|, max|beta|) of the GroupNorms (f16x3 bound)
     gb2: Tuple[float, float] = (0.0, 0.0)
-    w1wn: Optional[K.X6Weight] = None  # Winograd F(2,3) packs (precision 'f16x3', kernels.wino_enabled())
+    w1wn: Optional[K.X6Weight] = None  # Winograd F(2,3) packs (precision 'f16x3', forms.wino)
     w2wn: Optional[K.X6Weight] = None
 
 
@@ -130,11 +130,11 @@ class UnetEngine:
         self.model = model
         self.device = params[0].device
         self.precision = getattr(model, 'conv_precision', None) or K.default_conv_precision()
-        # f16x3 attention on the pre-split in-projection (WC_ATTN_PRESPLIT=0: fp32 projection + split
-        # in the attention kernel, the bit-identical reference path)
-        self.attn_presplit = os.environ.get('WC_ATTN_PRESPLIT', '1') != '0'
+        # f16x3 attention on the pre-split in-projection (off: fp32 projection + split in the attention
+        # kernel, the bit-identical reference path)
+        self.attn_presplit = forms.current().attn_presplit
         # GroupNorm statistics from the producers' epilogue tile partials (False: a stats pass per GN)
-        self.gn_partials = os.environ.get('WC_GN_PARTIALS', '1') != '0'
+        self.gn_partials = forms.current().gn_partials
         self._sig = self._signature()
         self._pack()
 
@@ -209,7 +209,7 @@ class UnetEngine:
             if f3:
                 p.w1f3 = K.pack_f16x3(p.w1, ci)
                 p.w2f3 = K.pack_f16x3(p.w2, co, ci, res_f16=True)  # residual bounded by GN1's stats of X
-                if K.wino_enabled():
+                if forms.current().wino:
                     p.w1wn = K.pack_wino(p.w1, ci)
                     p.w2wn = K.pack_wino(p.w2, co, ci)
                 p.gb1 = (float(p.g1.abs().max()), float(p.be1.abs().max()))
@@ -234,17 +234,17 @@ class UnetEngine:
 
     def _f3s(self, w: torch.Tensor, c0: int) -> Optional[K.X6Weight]:
         """f16x3 space-to-depth pack of a 4x4 / stride-2 down conv for wc_conv4x4s2_f16x3 (the halo
-        kernel), or None (outside f16x3 mode, N <= 64, or WC_DOWN_S2D=0: the implicit GEMM)."""
+        kernel), or None (outside f16x3 mode, N <= 64, or forms.down_s2d off: the implicit GEMM)."""
         if (self.precision != 'f16x3' or c0 % 16 or K.x6_tile(w.shape[0])[1] != 128
-                or os.environ.get('WC_DOWN_S2D', '1') == '0'):
+                or not forms.current().down_s2d):
             return None
         return K.pack_f16x3_s2d(w, c0)
 
     def _f3t(self, wt: torch.Tensor, c0: int) -> Optional[K.X6Weight]:
         """f16x3 pack of a 4x4 / stride-2 ConvTranspose for wc_convtr4x4s2_f16x3 (all four parities in
-        one launch of the halo kernel), or None (outside f16x3 mode or WC_UP_CT=0: the four
+        one launch of the halo kernel), or None (outside f16x3 mode or forms.up_ct off: the four
         implicit-GEMM parities)."""
-        if self.precision != 'f16x3' or c0 % 16 or os.environ.get('WC_UP_CT', '1') == '0':
+        if self.precision != 'f16x3' or c0 % 16 or not forms.current().up_ct:
             return None
         return K.pack_f16x3_convT(wt.detach().float())
 
@@ -399,7 +399,7 @@ class UnetEngine:
                 # the in_proj epilogue writes Q, K, V already scaled and split (fp16 pieces, V
                 # transposed in the PV key order); the attention copies K / V^T tiles by LDS-DMA
                 qkv3 = torch.empty(B * 6 * C * N, dtype=torch.int16, device=self.device)
-                if K.proj_pa_enabled() and K.proj_pa_ok(Y, 3 * C):
+                if forms.current().proj_pa and K.proj_pa_ok(Y, 3 * C):
                     # GN applied and split once per element (not once per 128-column N tile), then
                     # both GEMM operands staged by LDS-DMA
                     a3 = K.split_f16x3_tiled(Y, a_exp, sc, sh)
@@ -408,7 +408,7 @@ class UnetEngine:
                 else:
                     K.conv_igemm_f16x3_qkv(seg, p.w_in_f3, p.b_in, qkv3, Hm=H, Wm=W, a_exp=a_exp, C=C,
                                            heads=p.heads, exps=exps)
-                if K.proj_pa_enabled() and K.proj_pa_ok(Y, C) and C % 32 == 0:
+                if forms.current().proj_pa and K.proj_pa_ok(Y, C) and C % 32 == 0:
                     # the attention writes O already scaled and split in the out-projection's LDS
                     # stage order (no fp32 O round trip, no split pass); the GEMM copies it by LDS-DMA
                     a3o = K.attention_presplit_a3(qkv3, B, N, C, p.heads, exps)

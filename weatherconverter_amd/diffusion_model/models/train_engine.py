@@ -28,11 +28,11 @@ Precision bf16x6 / fp32: bf16x6 / fp32 MFMA throughout.  fp32-class gradients, c
 PyTorch autograd of the reference restatement in float64.  Every gradient buffer is written in a
 fixed order: results are deterministic run to run.
 """
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from ... import forms
 from ... import kernels as K
 from ...kernels import Seg, View
 from .engine import TAPS1, TAPS3, TAPS4S2, UnetEngine, pack_conv, pack_convT
@@ -106,7 +106,7 @@ class TrainEngine:
         self.precision = 'fp32' if p == 'fp32' else 'bf16x6'
         self.f3 = p == 'f16x3'
         # data gradients on f16x3 under per-image absmax bounds of the incoming gradient (mode f16x3)
-        self.f3d = self.f3 and K.dgrad_f16x3_enabled()
+        self.f3d = self.f3 and forms.current().dgrad_f16x3
         self.tape: List[tuple] = []
         self.last_tape: Optional[Tape] = None
 
@@ -135,9 +135,9 @@ class TrainEngine:
         ci, co = w1.shape[1], w1.shape[0]
         wr2 = wr.reshape(co, ci)
         f3 = self.f3 and ci % 16 == 0 and co % 16 == 0
-        wino = K.wino_enabled()
+        wino = forms.current().wino
         raw = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (w1, w2)) \
-            and 9 * (max(ci, co) + 4) * 4 <= 64 * 1024 and os.environ.get('WC_PACK_RAW', '1') != '0'
+            and 9 * (max(ci, co) + 4) * 4 <= 64 * 1024 and forms.current().pack_raw
         L = _Pack.lazy
         # shared re-layouts, each built once and only if a pack that needs it is (the Winograd forms
         # usually replace the direct f16x3 ones, so those are lazy too)
@@ -299,8 +299,8 @@ class TrainEngine:
                           tp[2].weight.detach().float().contiguous(), tp[2].bias.detach().float().contiguous()]
             rows = [rp for st in self.downs + self.mids + self.ups for rp in st[0]]
             # every ResBlock's Winograd packs (forward and data-gradient forms; the weights change each
-            # step) in one launch instead of one each (WC_PACK_BATCH=0: built lazily one by one)
-            if os.environ.get('WC_PACK_BATCH', '1') != '0':
+            # step) in one launch instead of one each (forms.pack_batch off: built lazily one by one)
+            if forms.current().pack_batch:
                 reqs = [(rp, k, r) for rp in rows for k, r in rp.get('_wino_raw', {}).items()]
                 for (rp, k, _), pk in zip(reqs, K.pack_wino_raw_batch([r for _, _, r in reqs])):
                     dict.__setitem__(rp, k, pk)
@@ -311,9 +311,9 @@ class TrainEngine:
             co = m.conv_out.weight.detach()  # [NO][C][3][3]
             NO, C = co.shape[0], co.shape[1]
             # the 3-channel head on its fp32 VALU kernels (wc_head_conv forward, wc_head_wgrad /
-            # wc_head_dgrad backward): an MFMA tile pads its 3 channels 20x (WC_TRAIN_SMALLCONV=0: the
-            # generic implicit GEMMs, kept for A/B)
-            self.head_small = K.smallconv_enabled() and NO == 3 and C in (32, 64)
+            # wc_head_dgrad backward): an MFMA tile pads its 3 channels 20x (forms.train_smallconv off:
+            # the generic implicit GEMMs, kept for A/B)
+            self.head_small = forms.current().train_smallconv and NO == 3 and C in (32, 64)
             if self.head_small:
                 self.head_wp = K.pack_head(co)
                 self.head_T = None
@@ -332,7 +332,7 @@ class TrainEngine:
         producer's epilogue when that is a split-precision conv, so its GroupNorm needs no stats pass."""
         t = self._new(B, H, W, C)
         sw = UnetEngine._sw(C)
-        if sw is not None and K.GnPart.eligible(t) and os.environ.get('WC_TRAIN_GN_PARTIALS', '1') != '0':
+        if sw is not None and K.GnPart.eligible(t) and forms.current().train_gn_partials:
             K.GnPart.attach(t, sw)
         return t
 
@@ -378,7 +378,7 @@ class TrainEngine:
         writer stores its values instead of adding them to a zero fill (no fill, no read of zeros)."""
         gv = self._gview(v)
         if id(gv.t) in self.gfresh and gv.c0 == 0 and gv.C == gv.t.shape[-1] \
-                and os.environ.get('WC_TRAIN_LAZY_GRAD', '1') != '0':
+                and forms.current().train_lazy_grad:
             self.gfresh.discard(id(gv.t))
             return gv, True
         return self._grad(v), False
@@ -404,11 +404,11 @@ class TrainEngine:
         return t
 
     def _bound(self, v: View, tracked: Optional[torch.Tensor]) -> torch.Tensor:
-        """The per-image bound a consumer uses: the writers' tracked bound (WC_CHECK_GBOUND=1: checked
+        """The per-image bound a consumer uses: the writers' tracked bound (forms.check_gbound: checked
         against a fresh absmax of the view, which it must not be below)."""
         if tracked is None:
             return K.absmax_images(v)
-        if os.environ.get('WC_CHECK_GBOUND', '0') == '1':
+        if forms.current().check_gbound:
             real = K.absmax_images(v)
             if bool((real > tracked).any()):
                 raise RuntimeError(f'gradient range bound below the values: {tracked.tolist()} < {real.tolist()}')
@@ -759,13 +759,13 @@ class TrainEngine:
         g2 = rp['gn2']
         ga2, be2 = g2.weight.detach().float(), g2.bias.detach().float()
         # dh's per-(image, channel) sums (conv1's bias / time-embedding gradients) in closed form from the
-        # GN backward's own sums (WC_TRAIN_DH_SUMS=0: a channel_sums pass over dh)
-        dh_sums = os.environ.get('WC_TRAIN_DH_SUMS', '1') != '0'
+        # GN backward's own sums (forms.train_dh_sums off: a channel_sums pass over dh)
+        dh_sums = forms.current().train_dh_sums
         pre2 = None
         if f3Y:
             if rp.has('wn_2T') and K.wino_eligible([Seg(gY, TAPS3)], co, H, W):
                 # GN2's backward sums of dz2 formed in the data-gradient conv's epilogue (no pass over dz2)
-                if K.gnb_epilogue_enabled():
+                if forms.current().train_gnb_epilogue:
                     pre2 = K.GnbSums.make(h, st2[2], st2[3], ga2, be2, True, dx_sums=dh_sums)
                 K.conv3x3_wino([Seg(gY, TAPS3)], rp['wn_2T'], None, dz2, Hm=H, Wm=W, a_exp=60, a_bound=bY, gnb=pre2)
             else:
@@ -799,7 +799,7 @@ class TrainEngine:
         pre1 = None
         if f3h:
             if rp.has('wn_1T') and K.wino_eligible([Seg(dh, TAPS3)], ci, H, W):
-                if K.gnb_epilogue_enabled():
+                if forms.current().train_gnb_epilogue:
                     pre1 = K.GnbSums.make(X, st1[2], st1[3], ga1, be1, True)
                 K.conv3x3_wino([Seg(dh, TAPS3)], rp['wn_1T'], None, dz1, Hm=H, Wm=W, a_exp=60, a_bound=bh, gnb=pre1)
             else:
@@ -903,7 +903,7 @@ class TrainEngine:
         g = self._grad(cur)
         self._bias_grad(g, m.conv_in.bias)
         w = m.conv_in.weight
-        if K.smallconv_enabled() and w.shape[1] == 3 and g.C in (32, 64) and self.x.is_contiguous():
+        if forms.current().train_smallconv and w.shape[1] == 3 and g.C in (32, 64) and self.x.is_contiguous():
             K.stem_wgrad(self.x, g, self._pgrad(w))  # fp32 VALU, the 3 input channels unpadded
             return
         xn = K.nchw_to_nhwc(self.x, 4)

@@ -16,6 +16,7 @@ from typing import Optional
 
 import torch
 
+from .. import forms
 from .config import Config, DiffusionConfig, ModelConfig, TrainingConfig, load_config  # noqa: F401
 from .models.unet_base import Unet
 from .scheduler.linear_noise_scheduler import LinearNoiseScheduler
@@ -84,16 +85,17 @@ class _GraphStep:
         # finalize, scheduler) under the other group's convs.  Same-box A/B at 256 px B=16, 60-step
         # bench, two rounds (profiles/r06_graph_split_ab.txt): 23.74 / 23.73 (1), 23.34 / 23.39 (2),
         # 24.09 / 24.14 (4) ms/step -- two groups by default where each keeps >= 8 images (rounds 1-5
-        # measured 1 vs 2 within box spread on slower kernels).  WC_GRAPH_SPLIT overrides.
+        # measured 1 vs 2 within box spread on slower kernels).  forms.graph_split overrides.
         B = x.shape[0]
         if split is None:
-            split = int(os.environ.get('WC_GRAPH_SPLIT', '2' if B >= 16 and B % 2 == 0 else '1'))
+            split = forms.current().graph_split
+            if split is None:
+                split = 2 if B >= 16 and B % 2 == 0 else 1
         self.split = split if split > 1 and B % split == 0 else 1
         self.streams = [torch.cuda.Stream(device=x.device) for _ in range(self.split - 1)]
         # concurrent groups: the pre-split convs with N % 256 == 0 on 8-wave workgroups, the form that
         # measured faster beside the other group's launches (slower alone: kernels.wino_vp_wide)
-        from ..kernels import wino_vp_wide
-        with wino_vp_wide(self.split > 1):
+        with forms.wino_vp_wide(self.split > 1):
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):

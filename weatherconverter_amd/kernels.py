@@ -5,18 +5,17 @@ All launches go on the current torch stream (so torch ops, HIP graphs captured t
 ever reaches a kernel; the C layer re-validates and returns a status that is turned into a
 RuntimeError.
 """
-import contextlib
 import ctypes
 import functools
-import os
 import threading
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from . import _native
+from . import _native, forms
 from ._native import ConvArgs, ConvSeg
+from .forms import CONV_PRECISIONS, wino_vp_wide  # noqa: F401  (kernels.wino_vp_wide: bench.py, _GraphStep)
 
 
 def _stream() -> int:
@@ -332,17 +331,11 @@ def conv_igemm(segs: Sequence[Seg], w: torch.Tensor, bias: Optional[torch.Tensor
 
 # ---- bf16x6 split-precision 3x3 conv (csrc/wc_conv6.hip) ----
 
-CONV_PRECISIONS = ('f16x3', 'bf16x6', 'fp32')
-
-
 def default_conv_precision() -> str:
     """Conv / attention arithmetic: 'f16x3' (the GN-prologue 3x3 convs on two-piece fp16 with a
     provable range bound, everything else bf16x6), 'bf16x6' (exact 3-piece bf16 split on bf16 MFMA
-    everywhere) or 'fp32' (fp32 MFMA).  All three are fp32-class.  Overridable with
-    WC_CONV_PRECISION."""
-    p = os.environ.get('WC_CONV_PRECISION', 'f16x3')
-    _req(p in CONV_PRECISIONS, f'WC_CONV_PRECISION must be one of {CONV_PRECISIONS}, got {p!r}')
-    return p
+    everywhere) or 'fp32' (fp32 MFMA).  All three are fp32-class.  The forms.conv_precision switch."""
+    return forms.current().conv_precision
 
 
 def _piece_dtype() -> torch.dtype:
@@ -418,20 +411,14 @@ def _pack_dev(w: torch.Tensor, C0: int, C1: int, ntaps: int, order: str, mode: i
     return data, wsinv
 
 
-def pack_device_enabled() -> bool:
-    """Weight packs built by the one-launch device kernel for CUDA weights; WC_PACK_DEVICE=0 keeps the
-    torch-op definitions (A/B, and the reference the kernel is tested against)."""
-    return os.environ.get('WC_PACK_DEVICE', '1') != '0'
-
-
 def pack_x6(w: torch.Tensor, C0: int, C1: int = 0, *, ntaps: int = 9, order: str = 'halo',
             device: Optional[bool] = None) -> X6Weight:
     """Re-pack a [N][ntaps*C0 + C1] conv weight (K = (tap, c) then the 1x1 residual columns, as
     engine.pack_conv) for the bf16x6 kernels.  order 'halo' (wc_conv3x3_x6, ntaps 9): steps are
     (16-channel chunk, tap) then the residual chunks; 'natural' (wc_conv_igemm_x6): K/16 in order.
-    A CUDA weight is packed by the device kernel (device=None: unless WC_PACK_DEVICE=0)."""
+    A CUDA weight is packed by the device kernel (device=None: unless forms.pack_device is off)."""
     N, K = w.shape
-    if (device if device is not None else pack_device_enabled()) and w.is_cuda:
+    if (device if device is not None else forms.current().pack_device) and w.is_cuda:
         _req(K == ntaps * C0 + C1 and C0 % 16 == 0 and C1 % 16 == 0, 'x6 weight shape')
         _req(order == 'natural' or ntaps == 9, "order 'halo' is for 3x3 weights")
         data, _ = _pack_dev(w, C0, C1, ntaps, order, 0, False)
@@ -469,7 +456,7 @@ def pack_f16x3(w: torch.Tensor, C0: int, C1: int = 0, *, ntaps: int = 9, order: 
     N, K = w.shape
     _req(K == ntaps * C0 + C1 and C0 % 16 == 0 and C1 % 16 == 0, 'f16x3 weight shape')
     _req(order == 'natural' or ntaps in (9, 4), "order 'halo' is for 3x3 (or s2d 2x2) weights")
-    if (device if device is not None else pack_device_enabled()) and w.is_cuda and amax is None:
+    if (device if device is not None else forms.current().pack_device) and w.is_cuda and amax is None:
         data, wsinv = _pack_dev(w, C0, C1, ntaps, order, 1, res_f16)
         order_tag = ('f16x3' if ntaps == 9 else 'f16x3s') if order == 'halo' else 'f16x3n'
         return X6Weight(data, N, x6_tile(N)[1], C0, C1, order_tag, wsinv, res_f16)
@@ -555,12 +542,6 @@ def wino_tile(N: int) -> Tuple[int, int]:
     return (16 if bn == 64 else 8), bn
 
 
-def wino_enabled() -> bool:
-    """ResBlock 3x3 convs through the Winograd F(2,3)-along-x kernel (WC_WINO=0: the direct halo
-    kernel, kept for A/B and as the reference the Winograd kernel is tested against)."""
-    return os.environ.get('WC_WINO', '1') != '0'
-
-
 def wino_filter(w: torch.Tensor, C0: int) -> torch.Tensor:
     """The F(2,3) filter transform of the 3x3 part of a [N][9*C0 (+ C1)] weight (K = (ky*3 + kx, c)),
     in float64: U[n][ky][p][c] = (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2) of row ky."""
@@ -635,13 +616,13 @@ def pack_wino(w: torch.Tensor, C0: int, C1: int = 0, *, device: Optional[bool] =
     power-of-two scale 2^sW[n] with max |U|, |w_res| * 2^sW <= 2^14, each value rounded once to fp32 and
     split into two round-to-nearest fp16 pieces; layout [N tile][C0/16][ky 3][p 4][piece][k-half][BN][8]
     then [N tile][C1/16][piece][k-half][BN][8].  A CUDA weight is packed by the device kernel (device=None:
-    unless WC_PACK_DEVICE=0)."""
+    unless forms.pack_device is off)."""
     N, K = w.shape
     _req(K == 9 * C0 + C1 and C0 % 16 == 0 and C1 % 16 == 0, 'wino weight shape')
     _, BN = wino_tile(N)
     Np = -(-N // BN) * BN
     T = Np // BN
-    if (device if device is not None else pack_device_enabled()) and w.is_cuda:
+    if (device if device is not None else forms.current().pack_device) and w.is_cuda:
         # one launch (wc_pack_wino), bit-identical to the definition below evaluated on the CPU
         data = torch.empty((T, (12 * C0 + C1) // 16 * 2 * 2 * BN * 8), dtype=torch.int16, device=w.device)
         wsinv = torch.empty(Np, dtype=torch.float32, device=w.device)
@@ -729,12 +710,6 @@ class GnbSums:
                               _ptr(self.beta), self.part.data_ptr(), _ptr(self.part3), self.splits, 0)
 
 
-def gnb_epilogue_enabled() -> bool:
-    """The training backward forms the GroupNorm-backward sums in the data-gradient conv's epilogue
-    (WC_TRAIN_GNB_EPI=0: a wc_gn_bwd_reduce pass over dz, A/B)."""
-    return os.environ.get('WC_TRAIN_GNB_EPI', '1') != '0'
-
-
 def conv3x3_wino(segs: Sequence[Seg], w: X6Weight, bias: Optional[torch.Tensor], out: View, *, Hm: int, Wm: int,
                  a_exp: int, a_bound: Optional[torch.Tensor] = None, temb: Optional[torch.Tensor] = None,
                  temb_ld: int = 0, res: Optional[View] = None, absmax: Optional[torch.Tensor] = None,
@@ -775,7 +750,7 @@ def conv3x3_wino(segs: Sequence[Seg], w: X6Weight, bias: Optional[torch.Tensor],
         vbuf = torch.empty(nb.value, dtype=torch.uint8, device=v.t.device)
         _timed('wino_vsplit_kernel', 'wc_wino_vsplit_f16x3', 0.0, ctypes.byref(a), int(a_exp), ab,
                vbuf.data_ptr(), nb.value, _stream(), nbytes=4.0 * v.B * Hm * Wm * v.C + nb.value)
-        wide = _WINO_VP_WIDE and BN == 128 and w.N % 256 == 0
+        wide = forms.wino_vp_wide_active() and BN == 128 and w.N % 256 == 0
         _timed(f'conv3x3_wino_kernel<{TH}, {256 if wide else BN}, 3, {"true" if len(segs) == 2 else "false"}>',
                'wc_conv3x3_wino_f16x3_vp8' if wide else 'wc_conv3x3_wino_f16x3_vp', _flops(segs, Hm, Wm, w.N) if prof else 0.0,
                ctypes.byref(a), w.data.data_ptr(), w.data.numel() * 2, int(a_exp), w.wsinv.data_ptr(), ab,
@@ -790,36 +765,10 @@ def conv3x3_wino(segs: Sequence[Seg], w: X6Weight, bias: Optional[torch.Tensor],
            mfma=wino_mfma_flops(segs, Hm, Wm, w.N))
 
 
-# Pre-split Winograd segment 0 (wc_wino_vsplit_f16x3) for convs with at least this many 128-channel
-# output tiles (the redundancy the in-conv prologue pays: every output tile re-transforms the halo);
-# 0 = never.  WC_WINO_VP sets it (A/B runs); set_wino_vsplit at run time.
-_WINO_VP_MIN_TILES = int(os.environ.get('WC_WINO_VP', '4'))
-
-
-# The pre-split convs with N % 256 == 0 on 8-wave 256-channel workgroups (wc_conv3x3_wino_f16x3_vp8):
-# set while a forward is captured beside another concurrent one (the two-group sampling graph), where
-# that form measured faster; alone the 4-wave form is (profiles/r06_wino_vp8_ab.txt).
-_WINO_VP_WIDE = False
-
-
-@contextlib.contextmanager
-def wino_vp_wide(on: bool = True):
-    """Inside the block the pre-split Winograd convs with N % 256 == 0 take the 8-wave form
-    (WC_WINO_VP8=0: never, A/B runs)."""
-    global _WINO_VP_WIDE
-    prev, _WINO_VP_WIDE = _WINO_VP_WIDE, bool(on) and os.environ.get('WC_WINO_VP8', '1') != '0'
-    try:
-        yield
-    finally:
-        _WINO_VP_WIDE = prev
-
-
 def set_wino_vsplit(min_tiles: int) -> int:
     """Use the pre-split Winograd form for GN+SiLU convs with >= min_tiles output-channel tiles of 128
-    (0 = never); returns the previous setting."""
-    global _WINO_VP_MIN_TILES
-    prev, _WINO_VP_MIN_TILES = _WINO_VP_MIN_TILES, int(min_tiles)
-    return prev
+    (0 = never): sets forms.wino_vp_min_tiles of the active Forms; returns the previous setting."""
+    return forms.replace(wino_vp_min_tiles=int(min_tiles)).wino_vp_min_tiles
 
 
 def wino_vsplit_wanted(segs: Sequence[Seg], N: int, Hm: int, Wm: int) -> bool:
@@ -827,7 +776,9 @@ def wino_vsplit_wanted(segs: Sequence[Seg], N: int, Hm: int, Wm: int) -> bool:
     wc_wino_vsplit_f16x3 checks (otherwise the in-conv prologue form runs, which accepts more shapes)."""
     s0 = segs[0]
     v = s0.view
-    return (_WINO_VP_MIN_TILES > 0 and N > 64 and -(-N // 128) >= _WINO_VP_MIN_TILES and s0.silu
+    # the threshold weighs the redundancy the in-conv prologue pays: every output tile re-transforms the halo
+    min_tiles = forms.current().wino_vp_min_tiles
+    return (min_tiles > 0 and N > 64 and -(-N // 128) >= min_tiles and s0.silu
             and s0.scale is not None and Wm % 16 == 0 and Wm <= 256 and v.W == Wm and v.H == Hm
             and v.C % 16 == 0 and v.ldc % 4 == 0 and v.ptr % 16 == 0)
 
@@ -887,7 +838,7 @@ def pack_f16x3_convT(wt: torch.Tensor) -> X6Weight:
     Ci, N = wt.shape[0], wt.shape[1]
     _req(Ci % 16 == 0, 'ConvT input channels % 16')
     parts = [pack_convT(wt, py, px)[1].to(wt.device) for py in (0, 1) for px in (0, 1)]
-    if pack_device_enabled() and wt.is_cuda and os.environ.get('WC_PACK_DEVICE_CONVT', '1') != '0':
+    if wt.is_cuda and forms.current().pack_device and forms.current().pack_device_convt:
         # one device pack of the four parities side by side, columns ordered (parity, chunk, tap, c%16):
         # its natural step order is then the stacked per-parity halo order below, and its per-row scale
         # the common one (the row max over all four parities) -- one launch instead of ~60 torch ops
@@ -968,12 +919,6 @@ def conv_igemm_f16x3_qkv(seg: Seg, w3: X6Weight, bias: Optional[torch.Tensor], q
            _flops([seg], Hm, Wm, w3.N) if _measuring() else 0.0, ctypes.byref(a), w3.data.data_ptr(),
            w3.data.numel() * 2, int(a_exp), w3.wsinv.data_ptr(), qkv3.data_ptr(), C, heads,
            ctypes.cast(ex, ctypes.c_void_p), _stream())
-
-
-def proj_pa_enabled() -> bool:
-    """Attention projections on a pre-split A operand (wc_split_f16x3_tiled + wc_proj_f16x3[_qkv]);
-    WC_PROJ_PA=0 keeps the register-staged implicit GEMM (for A/B measurement)."""
-    return os.environ.get('WC_PROJ_PA', '1') != '0'
 
 
 def proj_pa_ok(v: View, N: int) -> bool:
@@ -1258,12 +1203,6 @@ def head_conv(x: View, scale: torch.Tensor, shift: torch.Tensor, w_packed: torch
            bias.data_ptr(), NO, out.data_ptr(), _stream())
 
 
-def smallconv_enabled() -> bool:
-    """Training's 3-channel convs (the head's forward / weight / data gradient, the stem's weight
-    gradient) on their fp32 VALU kernels (WC_TRAIN_SMALLCONV=0: the generic implicit GEMMs, for A/B)."""
-    return os.environ.get('WC_TRAIN_SMALLCONV', '1') != '0'
-
-
 def head_dgrad(g: torch.Tensor, w: torch.Tensor, dz: View):
     """Data gradient of conv_out (unet_base.py:485) from the NCHW loss gradient g (B, NO, H, W): the
     transposed 3x3 conv into the NHWC view dz (C = conv_out.in_channels), fp32 (wc_head_dgrad)."""
@@ -1459,16 +1398,6 @@ def absmax_images(v: View) -> torch.Tensor:
     return out
 
 
-def dgrad_f16x3_enabled() -> bool:
-    """Training data gradients on f16x3 under per-image absmax bounds; WC_DGRAD_F16X3=0 keeps bf16x6."""
-    return os.environ.get('WC_DGRAD_F16X3', '1') != '0'
-
-
-def wgrad3_enabled() -> bool:
-    """The halo-tiled 3x3 weight gradient (wc_conv_wgrad3); WC_WGRAD3=0 keeps the generic GEMM (A/B)."""
-    return os.environ.get('WC_WGRAD3', '1') != '0'
-
-
 def wgrad3_ok(g: View, s0: Seg) -> bool:
     """Shapes wc_conv_wgrad3 takes: segment 0 a 3x3 stride-1 grid at the gradient's own grid, M % 64,
     C0 % 32 (% 64 when M % 128 != 0), W % 16, H % 8 (H % 2 for the 64-channel tiles)."""
@@ -1492,17 +1421,6 @@ class F3Bounds(NamedTuple):
 
 def _bound_ok(t: torch.Tensor, B: int) -> bool:
     return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= B
-
-
-def wgrad_f16x3_enabled() -> bool:
-    """The generic weight gradient on f16x3 when the caller supplies bounds (WC_WGRAD_F16X3=0: bf16x6)."""
-    return os.environ.get('WC_WGRAD_F16X3', '1') != '0'
-
-
-def wgrad3_f16x3_enabled() -> bool:
-    """The halo 3x3 weight gradient on f16x3 when the caller supplies the bounds (WC_WGRAD3_F16X3=0:
-    bf16x6, for A/B)."""
-    return os.environ.get('WC_WGRAD3_F16X3', '1') != '0'
 
 
 def conv_wgrad(g: View, segs: Sequence[Seg], dw0: torch.Tensor, s0: Tuple[int, int, int], *, Cw: Optional[int] = None,
@@ -1535,14 +1453,14 @@ def conv_wgrad(g: View, segs: Sequence[Seg], dw0: torch.Tensor, s0: Tuple[int, i
         _req(dw1 is not None and dw1.is_cuda and dw1.is_contiguous() and (g.C - 1) * s1 + C1 <= dw1.numel(),
              'dw1: the residual segment gradient')
     lib = _native.load()
-    if x6 and wgrad3_ok(g, segs[0]) and wgrad3_enabled():
+    if x6 and wgrad3_ok(g, segs[0]) and forms.current().wgrad3:
         # 3x3 segment on the halo-tiled kernel; the residual 1x1 segment (if any) as its own GEMM
         P = B * g.H * g.W
         splits = lib.wc_conv_wgrad3_splits(g.C, C0, B, g.H, g.W, 512)
         a.nseg = 1
         part = torch.empty(splits * g.C * K0, dtype=torch.float32, device=g.t.device)
         s = _stream()
-        if f3 is not None and segs[0].scale is not None and f3.x0 is None and wgrad3_f16x3_enabled():
+        if f3 is not None and segs[0].scale is not None and f3.x0 is None and forms.current().wgrad3_f16x3:
             _req(_bound_ok(f3.g, B), 'f3 bound: float32 [B] on the device')
             _timed('conv_wgrad3_kernel', 'wc_conv_wgrad3_f16x3', 2.0 * P * g.C * K0, ctypes.byref(a), part.data_ptr(),
                    splits, int(f3.x_exp0), f3.g.data_ptr(), s)
@@ -1560,7 +1478,7 @@ def conv_wgrad(g: View, segs: Sequence[Seg], dw0: torch.Tensor, s0: Tuple[int, i
     splits = lib.wc_conv_wgrad_splits(g.C, Kc, P, 2048)
     part = torch.empty(splits * g.C * Kc, dtype=torch.float32, device=g.t.device)
     s = _stream()
-    if (x6 and f3 is not None and wgrad_f16x3_enabled() and (C1 == 0 or f3.x1 is not None)
+    if (x6 and f3 is not None and forms.current().wgrad_f16x3 and (C1 == 0 or f3.x1 is not None)
             and (f3.x0 is not None or f3.x_exp0 < 60)):
         for t_ in (f3.g, f3.x0, f3.x1):
             _req(t_ is None or _bound_ok(t_, B), 'f3 bounds: float32 [B] on the device')
@@ -1618,10 +1536,6 @@ def channel_sums(g: View) -> torch.Tensor:
                  None, s)
     return sums
 
-
-# WC_ATTN_BWD192_FP32=1 (read once): the d = 192 dK / dV on the fp32-MFMA kernel; the C side follows the
-# dqkv_absmax argument alone (NULL selects the fp32 kernel), so the two sides cannot disagree
-_ATTN_BWD192_FP32 = os.environ.get('WC_ATTN_BWD192_FP32', '0') == '1'
 
 # The bsum deferral queue is per thread: autograd runs each device's backward on its own worker thread
 # (as _native's library selector), so two engines' backwards never share one queue.
@@ -1742,16 +1656,6 @@ def attention_fwd_lse(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, B
            out.data_ptr(), C, lse.data_ptr(), B, N, C, heads, float(d**-0.5), _stream())
 
 
-def attention_bwd6_enabled() -> bool:
-    """The bf16x6 attention backward (wc_attention_bwd6); WC_ATTN_BWD6=0 keeps fp32 MFMA (A/B)."""
-    return os.environ.get('WC_ATTN_BWD6', '1') != '0'
-
-
-def attention_bwd_f16x3_enabled() -> bool:
-    """The f16x3 attention backward when the caller supplies the bounds (WC_ATTN_BWD_F16X3=0: bf16x6, A/B)."""
-    return os.environ.get('WC_ATTN_BWD_F16X3', '1') != '0'
-
-
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, dqkv: torch.Tensor,
                   B: int, N: int, C: int, heads: int, precision: str = 'fp32', exps: Optional[Tuple[int, int, int]] = None,
                   dout_bound: Optional[torch.Tensor] = None, dqkv_absmax: Optional[torch.Tensor] = None) -> bool:
@@ -1768,18 +1672,20 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
     dv = torch.empty(B * heads * N, dtype=torch.float32, device=qkv.device)
     args = (qkv.data_ptr(), 3 * C, out.data_ptr(), C, dout.data_ptr(), C, lse.data_ptr(), dv.data_ptr(),
             dqkv.data_ptr(), 3 * C, B, N, C, heads, float(d**-0.5))
-    f3ok = precision == 'f16x3' and exps is not None and dout_bound is not None and attention_bwd_f16x3_enabled()
-    if d == 192 and f3ok and attention_bwd6_enabled():
+    f = forms.current()
+    f3ok = precision == 'f16x3' and exps is not None and dout_bound is not None and f.attn_bwd_f16x3
+    if d == 192 and f3ok and f.attn_bwd6:
         # dQ on f16x3 with the output dims in three parts; dK / dV on f16x3 with the V rows in LDS (or, with
-        # WC_ATTN_BWD192_FP32=1, on fp32 MFMA, which raises no bound)
+        # forms.attn_bwd192_fp32, on fp32 MFMA, which raises no bound: the C side follows the dqkv_absmax
+        # argument alone, NULL selects the fp32 kernel, so the two sides cannot disagree)
         _req(_bound_ok(dout_bound, B), 'dout_bound: float32 [B] on the device')
-        amx = dqkv_absmax if not _ATTN_BWD192_FP32 else None
+        amx = dqkv_absmax if not f.attn_bwd192_fp32 else None
         if amx is not None:
             _req(_bound_ok(amx, B), 'dqkv_absmax: float32 [B] on the device')
         _timed(f'attention_bwd<{d}>', 'wc_attention_bwd_f16x3', 10.0 * B * N * N * C, *args, int(exps[0]),
                int(exps[1]), int(exps[2]), dout_bound.data_ptr(), _ptr(amx), _stream())
         return amx is not None
-    if precision != 'fp32' and d in (32, 64, 128) and attention_bwd6_enabled():
+    if precision != 'fp32' and d in (32, 64, 128) and f.attn_bwd6:
         if f3ok:
             _req(dout_bound.is_cuda and dout_bound.dtype == torch.float32 and dout_bound.numel() >= B,
                  'dout_bound: float32 [B] on the device')
