@@ -23,7 +23,9 @@ class Forms:
     # conv / attention arithmetic: 'f16x3' (the GN-prologue 3x3 convs on two-piece fp16 under a provable
     # range bound, everything else bf16x6), 'bf16x6' (exact 3-piece bf16 split) or 'fp32' (fp32 MFMA)
     conv_precision: str = 'f16x3'
-    pack_device: bool = True  # CUDA weights packed by the one-launch device kernels (off: the torch-op definitions)
+    # CUDA weights packed by the one-launch device kernels (off: the torch-op definitions, the f16x3 / Winograd
+    # ones evaluated on the CPU: the same packs bit for bit)
+    pack_device: bool = True
     pack_device_convt: bool = True  # the ConvTranspose pack as one device pack of its four parities
     wino: bool = True  # ResBlock 3x3 convs on the Winograd F(2,3)-along-x kernel (off: the direct halo kernel)
     wino_vp_min_tiles: int = 4  # pre-split Winograd segment 0 from this many 128-channel output tiles; 0 = never

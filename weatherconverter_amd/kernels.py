@@ -8,7 +8,7 @@ RuntimeError.
 import ctypes
 import functools
 import threading
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -371,6 +371,11 @@ class X6Weight:
     res_f16: bool = False  # f16x3: the residual segment packed as fp16 pieces (needs an A bound)
 
 
+def _pack_on(p: X6Weight, device) -> X6Weight:
+    """A pack evaluated on the CPU, moved to the weight's device."""
+    return replace(p, data=p.data.to(device), wsinv=None if p.wsinv is None else p.wsinv.to(device))
+
+
 @functools.lru_cache(maxsize=None)
 def x6_tile(N: int) -> Tuple[int, int]:
     """(TH, BN) of wc_conv3x3_x6 for N output channels (mirrors wc_conv3x3_x6_tile_n)."""
@@ -396,7 +401,9 @@ def _pack_dev(w: torch.Tensor, C0: int, C1: int, ntaps: int, order: str, mode: i
     in exactly the layout of the torch definitions below, evaluated with IEEE fp32 arithmetic and
     round-to-nearest-even conversions — bit for bit the definitions run on the CPU
     (tests/test_gpu_train.py).  (The same torch ops run on the GPU are not: their fp16 / power-of-two
-    scaling ops differ in the last bit of some pieces, which the split tolerates.)"""
+    scaling ops differ in the last bit of some pieces, which the split tolerates; so with the device
+    pack switched off pack_f16x3 / pack_wino evaluate their definition of a CUDA weight on the CPU, and
+    forms.pack_device off is the bit-identical reference of on.)"""
     N, K = w.shape
     _, BN = x6_tile(N)
     Np = -(-N // BN) * BN
@@ -460,6 +467,9 @@ def pack_f16x3(w: torch.Tensor, C0: int, C1: int = 0, *, ntaps: int = 9, order: 
         data, wsinv = _pack_dev(w, C0, C1, ntaps, order, 1, res_f16)
         order_tag = ('f16x3' if ntaps == 9 else 'f16x3s') if order == 'halo' else 'f16x3n'
         return X6Weight(data, N, x6_tile(N)[1], C0, C1, order_tag, wsinv, res_f16)
+    if w.is_cuda:  # the definition is exact on the CPU only (_pack_dev): evaluated there, the pack moved back
+        return _pack_on(pack_f16x3(w.cpu(), C0, C1, ntaps=ntaps, order=order, res_f16=res_f16,
+                                   amax=None if amax is None else amax.cpu()), w.device)
     _, BN = x6_tile(N)
     Np = -(-N // BN) * BN
     T = Np // BN
@@ -630,6 +640,8 @@ def pack_wino(w: torch.Tensor, C0: int, C1: int = 0, *, device: Optional[bool] =
         _timed('pack_wino_kernel', 'wc_pack_wino', 0.0, wf.data_ptr(), N, C0, C1, data.data_ptr(), data.numel() * 2,
                wsinv.data_ptr(), _stream())
         return X6Weight(data, N, BN, C0, C1, 'wino', wsinv, bool(C1))
+    if w.is_cuda:  # as pack_f16x3: the definition evaluated on the CPU, where it is the device pack bit for bit
+        return _pack_on(pack_wino(w.cpu(), C0, C1), w.device)
     wd = torch.zeros((Np, K), dtype=torch.float64, device=w.device)
     wd[:N] = w.double()
     U = wino_filter(wd, C0)  # [Np][3][4][C0]
