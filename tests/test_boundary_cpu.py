@@ -47,6 +47,116 @@ def test_host_time_embedding_helper():
     assert e.shape == (2, 128) and torch.all(e[0, 64:] == 1)
 
 
+# ------------------------------------------------------------------ the supported envelope (engine.check_supported)
+def _mc(**overrides):
+    return ModelConfig(**{**MANIFEST['tiny']['config'], **overrides})
+
+
+@pytest.mark.parametrize('name', ['tiny', 'default_64', 'default_128', 'default_256'])
+@pytest.mark.parametrize('training', [False, True])
+@pytest.mark.parametrize('precision', ['f16x3', 'bf16x6', 'fp32'])
+def test_check_supported_accepts_golden_configs(name, training, precision):
+    from weatherconverter_amd.diffusion_model.models.engine import check_supported
+    check_supported(ModelConfig(**MANIFEST[name]['config']), precision, training)
+    if training:
+        check_supported(ModelConfig(**MANIFEST[name]['config']), 'f16', True)
+        check_supported(ModelConfig(**MANIFEST[name]['config']), 'bf16', True)
+
+
+def test_check_supported_accepts_the_shapes_matrix():
+    """Every case x precision tests/test_gpu_shapes.py runs is inside the envelope, and the ones it expects
+    to be rejected are outside, with the message naming the field."""
+    from test_gpu_shapes import CASES, PRECISIONS
+    from weatherconverter_amd.diffusion_model.models.engine import check_supported
+    rejected = []
+    for s in CASES:
+        mc = ModelConfig(**s.config)
+        for training, admitted in ((False, s.fwd), (True, s.train)):
+            for p in PRECISIONS:
+                if p in admitted:
+                    check_supported(mc, p, training)
+                else:
+                    with pytest.raises(RuntimeError, match=s.rejects):
+                        check_supported(mc, p, training)
+                    rejected.append((s.id, p, training))
+    assert sorted(rejected) == sorted([('ch48', p, tr) for p in PRECISIONS for tr in (False, True)] +
+                                      [('c6', p, True) for p in PRECISIONS])
+
+
+@pytest.mark.parametrize('overrides,precision,training,field,value', [
+    (dict(down_channels=[24, 64, 64, 128]), 'f16x3', False, 'down_channels', '24'),
+    (dict(down_channels=[24, 64, 64, 128]), 'bf16x6', True, 'down_channels', '24'),
+    (dict(down_channels=[32, 64, 64, 128], mid_channels=[128, 72, 64]), 'f16x3', False, 'mid_channels', '72'),
+    (dict(down_channels=[48, 96, 144, 144], mid_channels=[144, 144], num_heads=6), 'fp32', False, 'down_channels', '48'),
+    (dict(down_channels=[48, 96, 144, 144], mid_channels=[144, 144], num_heads=6), 'fp32', True, 'down_channels', '48'),
+    (dict(down_channels=[32, 64, 64, 160], mid_channels=[160, 160, 64]), 'f16x3', False, 'num_heads', 'head dim 40'),
+    (dict(down_channels=[32, 64, 64, 160], mid_channels=[160, 160, 64]), 'fp32', True, 'num_heads', 'head dim 40'),
+    (dict(down_channels=[48, 96, 144, 144], mid_channels=[144, 144], num_heads=6), 'f16x3', False, 'down_channels',
+     'GroupNorm'),
+    (dict(num_heads=3), 'f16x3', False, 'num_heads', 'must divide'),
+    (dict(time_emb_dim=260), 'f16x3', False, 'time_emb_dim', '260'),
+    (dict(time_emb_dim=258), 'f16x3', True, 'time_emb_dim', '258'),
+    (dict(im_channels=17), 'f16x3', False, 'im_channels', '17'),
+    (dict(im_channels=6), 'f16x3', True, 'im_channels', '6'),
+])
+def test_check_supported_rejects_naming_the_field(overrides, precision, training, field, value):
+    from weatherconverter_amd.diffusion_model.models.engine import check_supported
+    with pytest.raises(RuntimeError) as e:
+        check_supported(_mc(**overrides), precision, training)
+    assert f'{field} = ' in str(e.value) and value in str(e.value), str(e.value)
+
+
+def test_check_supported_reads_no_device(monkeypatch):
+    """Pure Python over the config: loading the native library or touching torch.cuda fails the call."""
+    from weatherconverter_amd import _native
+    from weatherconverter_amd.diffusion_model.models.engine import check_supported
+
+    def boom(*a, **k):
+        raise AssertionError('check_supported touched the device')
+
+    monkeypatch.setattr(_native, 'load', boom)
+    monkeypatch.setattr(_native, 'call', boom)
+    monkeypatch.setattr(torch.cuda, 'current_device', boom)
+    check_supported(_mc(), 'f16x3', True)
+
+
+def _csrc(name):
+    return open(os.path.join(ROOT, 'weatherconverter_amd', 'csrc', name)).read()
+
+
+def _cases(src: str, fn: str):
+    """The `case N:` / WC_BWD_CASE(N) labels of the first switch after `fn` in a csrc file."""
+    body = src[src.index(fn):]
+    body = body[re.search(r'switch \((D|C / heads)\)', body).start():]
+    body = body[:body.index('default:')]
+    return sorted(int(n) for n in re.findall(r'(?:case\s+|WC_BWD_CASE\()(\d+)', body))
+
+
+def test_envelope_constants_repeat_the_native_host_checks():
+    """check_supported's rules come from constants in kernels.py; each must equal the native check it repeats
+    (read from the source: the dispatch switches, BK, wc_temb's and wc_conv_in's limits)."""
+    from weatherconverter_amd import kernels as K
+    assert list(K.ATTN_FWD_DIMS) == _cases(_csrc('wc_attention.hip'), 'int attention_fwd_any(')
+    att6 = _csrc('wc_attention6.hip')
+    split = _cases(att6, 'launch_att6')
+    assert list(K.ATTN_SPLIT_DIMS) == split
+    # the pre-split forms dispatch over the same set
+    for m in re.finditer(r'switch \(C / heads\)(.*?)default:', att6, flags=re.S):
+        assert sorted(int(n) for n in re.findall(r'case\s+(\d+)', m.group(1))) == split
+    assert list(K.ATTN_BWD_DIMS) == _cases(_csrc('wc_attention_bwd.hip'), 'extern "C" int wc_attention_bwd(')
+    assert set(K.ATTN_BWD_DIMS) == set(K.ATTN_FWD_DIMS)  # whatever runs forward also trains
+    assert all(d % 8 == 0 for d in K.ATTN_BWD_DIMS)  # BwdCfg: DH = D / 2 read four floats at a time
+    assert re.search(r'constexpr int BK = (\d+);', _csrc('wc_conv.hip')).group(1) == str(K.IGEMM_BK)
+    misc = _csrc('wc_misc.hip')
+    assert f'D > {K.TEMB_MAX_D} || D % 4 != 0' in misc
+    assert f'Cin < 1 || Cin > {K.CONV_IN_MAX_CIN}' in misc and 'if (lds > 64 * 1024) return WC_E_SHAPE;' in misc
+    assert K.CONV_IN_MAX_LDS == 64 * 1024
+    assert f'(C / groups) % {K.GN_VEC} != 0' in _csrc('wc_gn.hip') and K.GN_GROUPS == 8
+    # the split-precision packs refuse what SPLIT_CK admits no more of
+    pk = open(os.path.join(ROOT, 'weatherconverter_amd', 'kernels.py')).read()
+    assert f'% {K.SPLIT_CK} == 0' in pk[pk.index('def pack_x6('):pk.index('def f16x3_a_exp(')]
+
+
 def _header_functions():
     src = open(os.path.join(ROOT, 'include', 'wc_kernels.h')).read()
     src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)

@@ -326,17 +326,25 @@ extern "C" int wc_attention_bwd(const float* qkv, int ld_qkv, const float* out, 
     hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, out, ld_out, dout,
                        ld_dout, B, N, heads, D, dv_work);
     WC_CHECK_LAUNCH();
+    // the instantiated head dims: kernels._ATTN_BWD_DIMS states the same set (tests/test_boundary_cpu.py
+    // compares the two).  BwdCfg pads a dim that is no multiple of 32 to DP; the pad columns are read
+    // inside the LDS slack and feed only accumulator rows d >= D, which are never stored.
+#define WC_BWD_CASE(DD)                                                                                              \
+    case DD: return launch_bwd<DD>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, s);
     switch (D) {
-        case 8: return launch_bwd<8>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, s);
-        case 16: return launch_bwd<16>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, s);
-        case 32: return launch_bwd<32>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, s);
-        case 64: return launch_bwd<64>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, s);
-        case 128:
-            return launch_bwd<128>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, s);
-        case 192:
-            return launch_bwd<192>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, s);
+        WC_BWD_CASE(8)
+        WC_BWD_CASE(16)
+        WC_BWD_CASE(24)
+        WC_BWD_CASE(32)
+        WC_BWD_CASE(48)
+        WC_BWD_CASE(64)
+        WC_BWD_CASE(96)
+        WC_BWD_CASE(128)
+        WC_BWD_CASE(160)
+        WC_BWD_CASE(192)
         default: return WC_E_SHAPE;
     }
+#undef WC_BWD_CASE
 }
 
 // Dv = rowsum(dO o O) per (image, head, query) only (the first step of the backward; used by the

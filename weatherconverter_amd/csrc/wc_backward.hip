@@ -869,7 +869,8 @@ __global__ __launch_bounds__(256) void time_embedding_kernel(const int64_t* __re
     const int half = D / 2;
     if (i >= nt * half) return;
     const int row = i / half, k = i - row * half;
-    const float f = powf(10000.0f, (float)k / (float)half);
+    // f_k correctly rounded, exactly as temb_kernel (wc_misc.hip) computes it: see there
+    const float f = (float)pow(10000.0, (double)((float)k / (float)half));
     const float a = (float)t[row] / f;
     out[(long)row * D + k] = sinf(a);
     out[(long)row * D + k + half] = cosf(a);

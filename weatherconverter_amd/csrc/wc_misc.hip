@@ -10,7 +10,7 @@ namespace {
 // --------------------------------------------------------------------------------------------
 // Time embedding (reference get_time_embedding unet_base.py:7-30; t_proj :395-397;
 // t_emb_layers :98-100 = SiLU -> Linear).  One launch computes, per timestep row,
-//   e = [sin(t/f_k), cos(t/f_k)],  f_k = 10000^(k/(D/2))   (fp32 pow/sin/cos as torch)
+//   e = [sin(t/f_k), cos(t/f_k)],  f_k = 10000^(k/(D/2))   (f_k rounded once to fp32; fp32 sin/cos)
 //   h = W2 SiLU(W1 e + b1) + b2                              (t_proj)
 //   out[p] = proj_w[p] . SiLU(h) + proj_b[p]                 (all ResBlock projections)
 // Every workgroup recomputes the 2x D^2 MLP (cheap) and owns 256 projection rows.
@@ -30,7 +30,10 @@ __global__ __launch_bounds__(TE_THREADS) void temb_kernel(const int64_t* __restr
     const int half = D / 2;
     const float tv = (float)t[row];
     for (int k = threadIdx.x; k < half; k += TE_THREADS) {
-        float f = powf(10000.0f, (float)k / (float)half);
+        // f_k correctly rounded (double pow of the recipe's fp32 exponent, rounded once): powf is only
+        // within an ulp or two, and one ulp of f_k moves t / f_k by up to 6e-5 at t = 999 (sin / cos follow).
+        // time_embedding_kernel (wc_backward.hip) evaluates the same expressions: the two agree bit for bit.
+        float f = (float)pow(10000.0, (double)((float)k / (float)half));
         float a = tv / f;
         e[k] = sinf(a);
         e[k + half] = cosf(a);

@@ -119,6 +119,68 @@ class AttnPack:
     gb: Tuple[float, float] = (0.0, 0.0)
 
 
+TRAIN_MAX_IM_CHANNELS = 4  # TrainEngine pads the image and the loss gradient to 4 NHWC channels
+
+
+def check_supported(mc, precision: str, training: bool = False) -> None:
+    """The configurations the engines run, stated once ("Supported configurations").
+    Pure Python over the ModelConfig: no device is read and nothing is launched.  UnetEngine and
+    TrainEngine call it before anything is packed, so a configuration outside the envelope raises here,
+    naming the field, the value and the rule, instead of part-way through a pass with a bare shape
+    status.  precision: 'f16x3' / 'bf16x6' / 'fp32' (training also 'f16' / 'bf16', the 16-bit lines on
+    the f16x3 kernels)."""
+    if precision not in K.CONV_PRECISIONS + ('f16', 'bf16'):
+        raise RuntimeError(f'weatherconverter_amd: unknown precision {precision!r}')
+
+    def bad(field, value, rule):
+        raise RuntimeError(f'weatherconverter_amd: unsupported configuration: {field} = {value!r}: {rule} '
+                           f'(precision {precision!r}, {"training" if training else "inference"})')
+
+    dc, mids = list(mc.down_channels), list(mc.mid_channels)
+    # channel counts: every conv's input segments are whole K-steps of its GEMM, and every GroupNorm(8)
+    # group is whole 4-channel reads of the statistics pass
+    gemm = K.IGEMM_BK if precision == 'fp32' else K.SPLIT_CK
+    gn = K.GN_GROUPS * K.GN_VEC
+    for field, chans in (('down_channels', dc), ('mid_channels', mids)):
+        for c in chans:
+            if c <= 0 or c % gemm:
+                bad(field, chans, f'every channel count must be a positive multiple of {gemm} (got {c}): ' +
+                    (f'the fp32 implicit GEMM reads {K.IGEMM_BK} channels per K-step' if precision == 'fp32' else
+                     f'the split-precision weight packs hold {K.SPLIT_CK} channels per K-step'))
+            if c % gn:
+                bad(field, chans, f'every channel count must be a multiple of {gn} (got {c}): GroupNorm({K.GN_GROUPS}) '
+                    f'statistics read each group {K.GN_VEC} channels at a time')
+    # attention head dims: downs / ups by the placement rule of Unet.level_has_attn, every mid block
+    L = len(dc) - 1
+    attn_c = [mids[j + 1] for j in range(len(mids) - 1)]
+    for i in range(L):
+        if (mc.im_size // (2**i)) in list(mc.attn_resolutions):
+            attn_c += [dc[i + 1], dc[i - 1] if i != 0 else dc[0]]
+    heads = mc.num_heads
+    for c in attn_c:
+        if heads <= 0 or c % heads:
+            bad('num_heads', heads, f'must divide the attention width {c}')
+        d = c // heads
+        rule = f'an attention layer of {c} channels has head dim {d}'
+        if d not in K.ATTN_FWD_DIMS:
+            bad('num_heads', heads, f'{rule}; the attention kernels exist for head dims {K.ATTN_FWD_DIMS}')
+        if precision != 'fp32' and d % 32 == 0 and d not in K.ATTN_SPLIT_DIMS:
+            bad('num_heads', heads, f'{rule}; the split-precision attention exists for {K.ATTN_SPLIT_DIMS}')
+        if training and d not in K.ATTN_BWD_DIMS:
+            bad('num_heads', heads, f'{rule}; the attention backward exists for head dims {K.ATTN_BWD_DIMS}')
+    D = mc.time_emb_dim
+    if D <= 0 or D % 4 or D > K.TEMB_MAX_D:
+        bad('time_emb_dim', D, f'must be a multiple of 4 and at most {K.TEMB_MAX_D} (wc_temb keeps the embedding '
+            'and the hidden layer in LDS and reads the weights four at a time)')
+    ci = mc.im_channels
+    if ci < 1 or ci > K.CONV_IN_MAX_CIN or ci * 9 * dc[0] * 4 > K.CONV_IN_MAX_LDS:
+        bad('im_channels', ci, f'the stem conv takes 1 to {K.CONV_IN_MAX_CIN} image channels and stages '
+            f'im_channels * 9 * down_channels[0] weights in at most {K.CONV_IN_MAX_LDS} bytes of LDS')
+    if training and ci > TRAIN_MAX_IM_CHANNELS:
+        bad('im_channels', ci, f'training takes at most {TRAIN_MAX_IM_CHANNELS} image channels: the stem and head '
+            f'weight gradients read the image and the loss gradient padded to {TRAIN_MAX_IM_CHANNELS} channels')
+
+
 class UnetEngine:
 
     def __init__(self, model):
@@ -126,6 +188,7 @@ class UnetEngine:
         if not params or not params[0].is_cuda:
             raise RuntimeError('weatherconverter_amd.Unet runs on the GPU only (HIP kernels, no CPU fallback): '
                                'move the model to a ROCm device first')
+        check_supported(model.model_config, getattr(model, 'conv_precision', None) or K.default_conv_precision())
         K._native.load()
         self.model = model
         self.device = params[0].device

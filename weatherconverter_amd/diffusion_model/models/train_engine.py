@@ -35,7 +35,7 @@ import torch
 from ... import forms
 from ... import kernels as K
 from ...kernels import Seg, View
-from .engine import TAPS1, TAPS3, TAPS4S2, UnetEngine, pack_conv, pack_convT
+from .engine import TAPS1, TAPS3, TAPS4S2, UnetEngine, check_supported, pack_conv, pack_convT
 
 _PARITIES = ((0, 0), (0, 1), (1, 0), (1, 1))
 
@@ -89,11 +89,12 @@ class TrainEngine:
         params = list(model.parameters())
         if not params or not params[0].is_cuda:
             raise RuntimeError('weatherconverter_amd.Unet trains on the GPU only (HIP kernels, no CPU fallback)')
+        p = (precision or getattr(model, 'train_precision', None) or getattr(model, 'conv_precision', None)
+             or K.default_conv_precision())
+        check_supported(model.model_config, p, training=True)
         K._native.load()
         self.model = model
         self.device = params[0].device
-        p = (precision or getattr(model, 'train_precision', None) or getattr(model, 'conv_precision', None)
-             or K.default_conv_precision())
         # 'f16': the 16-bit training line — the f16x3 arithmetic of mode f16x3 run on the single-piece
         # build (one fp16 piece per operand: wc_x6.hpp mfma_f16c), every kernel call routed to it
         # 'bf16': the same on the bf16 single-piece build (one bf16 piece per operand on the bf16 MFMA:

@@ -18,6 +18,20 @@ from ._native import ConvArgs, ConvSeg
 from .forms import CONV_PRECISIONS, wino_vp_wide  # noqa: F401  (kernels.wino_vp_wide: bench.py, _GraphStep)
 
 
+# The shape limits the native host checks enforce, as the constants engine.check_supported states the
+# supported configurations from (tests/test_boundary_cpu.py compares each with the csrc/ source it repeats).
+ATTN_FWD_DIMS = (8, 16, 24, 32, 48, 64, 96, 128, 160, 192)  # wc_attention.hip: attention_fwd_any
+ATTN_SPLIT_DIMS = (32, 64, 96, 128, 160, 192)  # wc_attention6.hip: the split-precision forward (head dim % 32 == 0)
+ATTN_BWD_DIMS = (8, 16, 24, 32, 48, 64, 96, 128, 160, 192)  # wc_attention_bwd.hip: wc_attention_bwd
+IGEMM_BK = 32  # wc_conv.hip: channels per K-step of the fp32 implicit GEMM (every segment's C % BK == 0)
+SPLIT_CK = 16  # channels per K-step of the split-precision packs (pack_x6 / pack_f16x3: C % 16 == 0)
+GN_GROUPS = 8  # the model's GroupNorm(8, C)
+GN_VEC = 4  # wc_gn.hip wc_gn_stats: a group's channels are read four at a time, (C / groups) % 4 == 0
+TEMB_MAX_D = 256  # wc_misc.hip wc_temb: D <= 256 and D % 4 == 0
+CONV_IN_MAX_CIN = 16  # wc_misc.hip wc_conv_in: 1 <= Cin <= 16, Cout % 4 == 0, Cin * 9 * Cout floats <= 64 KiB of LDS
+CONV_IN_MAX_LDS = 64 * 1024
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -1672,7 +1686,7 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
                   B: int, N: int, C: int, heads: int, precision: str = 'fp32', exps: Optional[Tuple[int, int, int]] = None,
                   dout_bound: Optional[torch.Tensor] = None, dqkv_absmax: Optional[torch.Tensor] = None) -> bool:
     """d qkv (same [q | k | v] rows as qkv) of softmax(Q K^T / sqrt(d)) V from the forward's output and lse:
-    fp32 MFMA (wc_attention_bwd), or with precision 'bf16x6' / 'f16x3' and a head dim in {32, 64, 128}
+    fp32 MFMA (wc_attention_bwd: head dims ATTN_BWD_DIMS), or with precision 'bf16x6' / 'f16x3' and a head dim in {32, 64, 128}
     (f16x3 also 192) the split-precision kernels: f16x3 (wc_attention_bwd_f16x3) when the Q / K / V exponents of the
     forward (exps) and the per-image max |dout| (dout_bound, device float32 [B]) are given, else
     bf16x6 (wc_attention_bwd6).  dqkv_absmax: float32 [B] raised to the max |dqkv| written per image
