@@ -181,6 +181,15 @@ def test_c_abi_library_exports_every_header_symbol():
     assert sorted(_native.EXPORTS) == names
 
 
+def test_every_header_function_has_a_derived_signature():
+    """_header_functions() finds the names with a regex of its own; the header reader must have bound exactly
+    those (a prototype it missed would be called with ctypes' default types)."""
+    from weatherconverter_amd import _native
+    names = _header_functions()
+    assert len(names) == 88 and sorted(_native.ABI.functions) == names
+    assert all(isinstance(a, list) and r is not None for r, a in _native.ABI.functions.values())
+
+
 def test_library_refuses_sources_other_than_the_trees(tmp_path, monkeypatch):
     """The library carries the digest of the sources it was built from; the loader compares it with the
     tree's and refuses a mismatch (one flipped byte in a copy of csrc/ is enough)."""

@@ -1,5 +1,9 @@
 """ctypes binding of ``libwc_kernels.so`` (the C ABI declared in ``include/wc_kernels.h``).
 
+The header is the one declaration of the ABI: the constants, the struct classes and every function's
+argument and return types below are read from its text (``_abi.read``) when this module is imported;
+nothing here repeats a signature, a field or a value.
+
 There is deliberately no CPU fallback: every product entry point goes through these kernels and a
 missing or failing library raises.  ``torch`` is imported before the library is opened so the HIP
 runtime torch ships (soname ``libamdhip64.so.7``) is the one the kernels bind to.
@@ -11,160 +15,17 @@ import threading
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-from . import _build, forms
+from . import _abi, _build, forms
 
-MAX_TAPS = 16
-NOISE_NONE, NOISE_TENSOR, NOISE_PHILOX = 0, 1, 2
+ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_kernels.h')).read())  # once per process
 
-EXPORTS = [
-    'wc_conv_igemm', 'wc_conv3x3_x6', 'wc_conv3x3_f16x3', 'wc_conv3x3_wino_f16x3', 'wc_conv3x3_wino_tile_n', 'wc_wino_vsplit_bytes', 'wc_wino_vsplit_f16x3', 'wc_conv3x3_wino_f16x3_vp', 'wc_conv3x3_wino_f16x3_vp8', 'wc_conv3x3_wino_gnb_splits', 'wc_conv3x3_wino_f16x3_gnb', 'wc_pack_wino', 'wc_pack_wino_raw', 'wc_pack_wino_batch', 'wc_conv3x3_x6_tile_n', 'wc_conv_igemm_x6',
-    'wc_conv_igemm_f16x3', 'wc_conv4x4s2_f16x3', 'wc_convtr4x4s2_f16x3', 'wc_conv_igemm_f16x3_qkv', 'wc_split_f16x3_tiled', 'wc_attention_fwd_f16x3_presplit_a3', 'wc_proj_f16x3', 'wc_proj_f16x3_qkv', 'wc_proj_set_tile', 'wc_attention_fwd_f16x3_presplit',
-    'wc_gn_num_splits',
-    'wc_gn_stats', 'wc_gn_finalize', 'wc_gn_finalize_bound', 'wc_gn_partials', 'wc_gn_finalize_part', 'wc_attention_fwd', 'wc_attention_fwd_x6', 'wc_attention_fwd_f16x3',
-    'wc_temb', 'wc_conv_in', 'wc_conv_in_gn', 'wc_head_conv', 'wc_ddpm_step', 'wc_add_noise', 'wc_philox_normal', 'wc_sgg_update',
-    'wc_avgpool2x2', 'wc_upsample2x_bilinear', 'wc_layernorm_channels', 'wc_noise_embed',
-    'wc_mse_workspace_doubles', 'wc_mse_loss', 'wc_dwconv', 'wc_version', 'wc_source_hash',
-    'wc_conv_wgrad', 'wc_conv_wgrad_x6', 'wc_conv_wgrad_f16x3', 'wc_conv_wgrad_splits', 'wc_wgrad_reduce', 'wc_gn_bwd_splits', 'wc_gn_bwd_reduce',
-    'wc_gn_bwd_finalize', 'wc_bsum', 'wc_bsum_batch', 'wc_gn_bwd_apply', 'wc_attention_fwd_lse', 'wc_attention_bwd', 'wc_gemm_small',
-    'wc_silu', 'wc_colsum', 'wc_time_embedding', 'wc_nchw_to_nhwc', 'wc_last_kernel_name', 'wc_stamp', 'wc_wall_clock_khz',
-    'wc_attention_fwd_f16x3_lse', 'wc_attention_fwd_x6_lse',
-    'wc_conv_wgrad3', 'wc_conv_wgrad3_f16x3', 'wc_conv_wgrad3_splits', 'wc_absmax_images', 'wc_attention_bwd6', 'wc_attention_bwd_f16x3', 'wc_attention_bwd_dkdv192', 'wc_attention_bwd_prep', 'wc_pack_split',
-    'wc_small_wgrad_workspace', 'wc_head_dgrad', 'wc_head_wgrad', 'wc_stem_wgrad'
-]
-ACT_NONE, ACT_GELU, ACT_SILU, ACT_PRELU, ACT_TANH01 = 0, 1, 2, 3, 4
-
-
-class ConvSeg(ctypes.Structure):
-    _fields_ = [
-        ('src', ctypes.c_void_p), ('C', ctypes.c_int), ('ldc', ctypes.c_int), ('H', ctypes.c_int),
-        ('W', ctypes.c_int), ('sy', ctypes.c_int), ('sx', ctypes.c_int), ('ntaps', ctypes.c_int),
-        ('dy', ctypes.c_int * MAX_TAPS), ('dx', ctypes.c_int * MAX_TAPS), ('scale', ctypes.c_void_p),
-        ('shift', ctypes.c_void_p), ('silu', ctypes.c_int), ('kbase', ctypes.c_int)
-    ]
-
-
-class GnbEpi(ctypes.Structure):
-    """wc_gnb_epi (include/wc_kernels.h): the GroupNorm-backward sums a data-gradient conv's epilogue forms."""
-    _fields_ = [('x', ctypes.c_void_p), ('ldx', ctypes.c_int), ('silu', ctypes.c_int), ('sc0', ctypes.c_void_p),
-                ('sh0', ctypes.c_void_p), ('gamma', ctypes.c_void_p), ('beta', ctypes.c_void_p),
-                ('part', ctypes.c_void_p), ('part3', ctypes.c_void_p), ('splits', ctypes.c_int), ('pad', ctypes.c_int)]
-
-
-class ConvArgs(ctypes.Structure):
-    _fields_ = [
-        ('seg', ConvSeg * 2), ('nseg', ctypes.c_int), ('B', ctypes.c_int), ('Hm', ctypes.c_int),
-        ('Wm', ctypes.c_int), ('N', ctypes.c_int), ('w', ctypes.c_void_p), ('ldw', ctypes.c_int),
-        ('bias', ctypes.c_void_p), ('temb', ctypes.c_void_p), ('temb_ld', ctypes.c_int),
-        ('res', ctypes.c_void_p), ('ldres', ctypes.c_int), ('out', ctypes.c_void_p),
-        ('ldo', ctypes.c_int), ('Ho', ctypes.c_int), ('Wo', ctypes.c_int), ('osy', ctypes.c_int),
-        ('osx', ctypes.c_int), ('ooy', ctypes.c_int), ('oox', ctypes.c_int),
-        ('out_nchw', ctypes.c_int), ('act', ctypes.c_int), ('absmax_out', ctypes.c_void_p),
-        ('act_param', ctypes.c_void_p), ('gn_part', ctypes.c_void_p), ('gn_ncb', ctypes.c_int),
-        ('gn_sw', ctypes.c_int), ('gn_c0', ctypes.c_int), ('gn_p64', ctypes.c_int), ('gn_np64', ctypes.c_int)
-    ]
-
-
-class WgradArgs(ctypes.Structure):
-    _fields_ = [
-        ('g', ctypes.c_void_p), ('M', ctypes.c_int), ('ldg', ctypes.c_int), ('seg', ConvSeg * 2),
-        ('nseg', ctypes.c_int), ('B', ctypes.c_int), ('Hm', ctypes.c_int), ('Wm', ctypes.c_int)
-    ]
-
-
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_L = ctypes.c_int64
-_F = ctypes.c_float
-_D = ctypes.c_double
-_U = ctypes.c_uint64
-
-_SIGS = {
-    'wc_conv_igemm': [ctypes.POINTER(ConvArgs), _P],
-    'wc_conv3x3_x6': [ctypes.POINTER(ConvArgs), _P, _L, _P],
-    'wc_conv3x3_x6_tile_n': [_I],
-    'wc_proj_set_tile': [_I],
-    'wc_conv3x3_f16x3': [ctypes.POINTER(ConvArgs), _P, _L, _I, _P, _P, _P],
-    'wc_conv3x3_wino_f16x3': [ctypes.POINTER(ConvArgs), _P, _L, _I, _P, _P, _P],
-    'wc_wino_vsplit_bytes': [_I, _I, _I, _I, _P],
-    'wc_wino_vsplit_f16x3': [ctypes.POINTER(ConvArgs), _I, _P, _P, _L, _P],
-    'wc_conv3x3_wino_f16x3_vp': [ctypes.POINTER(ConvArgs), _P, _L, _I, _P, _P, _P, _L, _P],
-    'wc_conv3x3_wino_f16x3_vp8': [ctypes.POINTER(ConvArgs), _P, _L, _I, _P, _P, _P, _L, _P],
-    'wc_conv3x3_wino_tile_n': [_I],
-    'wc_conv3x3_wino_gnb_splits': [_I, _I, _I],
-    'wc_conv3x3_wino_f16x3_gnb': [ctypes.POINTER(ConvArgs), _P, _L, _I, _P, _P, ctypes.POINTER(GnbEpi), _P],
-    'wc_pack_wino': [_P, _I, _I, _I, _P, _L, _P, _P],
-    'wc_pack_wino_raw': [_P, _P, _I, _I, _I, _I, _P, _L, _P, _P],
-    'wc_pack_wino_batch': [_P, _I, _I, _I, _P],
-    'wc_conv_igemm_x6': [ctypes.POINTER(ConvArgs), _P, _L, _P],
-    'wc_conv_igemm_f16x3': [ctypes.POINTER(ConvArgs), _P, _L, _I, _P, _P, _P],
-    'wc_conv4x4s2_f16x3': [ctypes.POINTER(ConvArgs), _P, _L, _P, _P, _P],
-    'wc_convtr4x4s2_f16x3': [ctypes.POINTER(ConvArgs), _P, _L, _P, _P, _P],
-    'wc_conv_igemm_f16x3_qkv': [ctypes.POINTER(ConvArgs), _P, _L, _I, _P, _P, _I, _I, _P, _P],
-    'wc_split_f16x3_tiled': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _L, _P],
-    'wc_attention_fwd_f16x3_presplit_a3': [_P, _P, _L, _I, _I, _I, _I, _F, _I, _I, _I, _P],
-    'wc_proj_f16x3': [ctypes.POINTER(ConvArgs), _P, _L, _P, _L, _I, _P, _P],
-    'wc_proj_f16x3_qkv': [ctypes.POINTER(ConvArgs), _P, _L, _P, _L, _I, _P, _P, _I, _I, _P, _P],
-    'wc_attention_fwd_f16x3_presplit': [_P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _P],
-    'wc_gn_num_splits': [_I, _I, _I],
-    'wc_stamp': [_P, _I, _P],
-    'wc_wall_clock_khz': [_P],
-    'wc_gn_stats': [_P, _I, _I, _I, _I, _I, _P, _P],
-    'wc_gn_finalize': [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P],
-    'wc_gn_finalize_bound': [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P],
-    'wc_gn_partials': [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
-    'wc_gn_finalize_part': [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P],
-    'wc_attention_fwd': [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P],
-    'wc_attention_fwd_x6': [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P],
-    'wc_attention_fwd_f16x3': [_P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _P],
-    'wc_attention_fwd_f16x3_lse': [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _I, _I, _P],
-    'wc_attention_fwd_x6_lse': [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P],
-    'wc_temb': [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    'wc_conv_in': [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P],
-    'wc_conv_in_gn': [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _P],
-    'wc_head_conv': [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P],
-    'wc_ddpm_step': [_P, _P, _P, _P, _P, _L, _L, _F, _F, _F, _F, _I, _U, _L, _L, _P],
-    'wc_add_noise': [_P, _P, _P, _P, _P, _L, _L, _P],
-    'wc_philox_normal': [_P, _L, _L, _U, _L, _L, _P],
-    'wc_sgg_update': [_P, _P, _P, _P, _P, _I, _I, _F, _D, _D, _D, _I, _P],
-    'wc_avgpool2x2': [_P, _I, _P, _I, _I, _I, _I, _I, _P],
-    'wc_upsample2x_bilinear': [_P, _I, _P, _I, _I, _I, _I, _I, _P],
-    'wc_layernorm_channels': [_P, _I, _P, _P, _F, _P, _I, _L, _I, _P],
-    'wc_noise_embed': [_P, _P, _I, _P, _I, _I, _I, _P],
-    'wc_mse_workspace_doubles': [],
-    'wc_mse_loss': [_P, _P, _L, _P, _F, _P, _P, _P],
-    'wc_dwconv': [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
-    'wc_small_wgrad_workspace': [_I, _I, _I, _I],
-    'wc_head_dgrad': [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P],
-    'wc_head_wgrad': [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _I, _P],
-    'wc_stem_wgrad': [_P, _I, _P, _I, _I, _I, _I, _I, _P, _L, _P, _I, _P],
-    'wc_conv_wgrad': [ctypes.POINTER(WgradArgs), _P, _I, _P],
-    'wc_conv_wgrad_x6': [ctypes.POINTER(WgradArgs), _P, _I, _P],
-    'wc_conv_wgrad_f16x3': [ctypes.POINTER(WgradArgs), _P, _I, _P, _I, _P, _P, _P],
-    'wc_conv_wgrad_splits': [_I, _I, _L, _I],
-    'wc_conv_wgrad3': [ctypes.POINTER(WgradArgs), _P, _I, _P],
-    'wc_conv_wgrad3_f16x3': [ctypes.POINTER(WgradArgs), _P, _I, _I, _P, _P],
-    'wc_conv_wgrad3_splits': [_I, _I, _I, _I, _I, _I],
-    'wc_absmax_images': [_P, _I, _I, _I, _I, _P, _P],
-    'wc_attention_bwd6': [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    'wc_attention_bwd_f16x3': [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _P, _P, _P],
-    'wc_attention_bwd_dkdv192': [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    'wc_attention_bwd_prep': [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P],
-    'wc_pack_split': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P],
-    'wc_wgrad_reduce': [_P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _L, _P, _L, _I, _P],
-    'wc_gn_bwd_splits': [_I, _I],
-    'wc_gn_bwd_reduce': [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    'wc_gn_bwd_finalize': [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    'wc_bsum': [_P, _I, _I, _I, _P, _I, _P],
-    'wc_bsum_batch': [_P, _I, _I, _I, _P],
-    'wc_gn_bwd_apply': [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _P, _P],
-    'wc_attention_fwd_lse': [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P],
-    'wc_attention_bwd': [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    'wc_gemm_small': [_I, _I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _F, _F, _P],
-    'wc_silu': [_P, _P, _P, _L, _I, _P],
-    'wc_colsum': [_P, _I, _I, _L, _P, _I, _P],
-    'wc_time_embedding': [_P, _I, _I, _P, _P],
-    'wc_nchw_to_nhwc': [_P, _I, _I, _I, _I, _P, _I, _P],
-}
+EXPORTS = list(ABI.functions)
+ConvSeg, ConvArgs, GnbEpi, WgradArgs, WinoPackJob, BsumJob = (ABI.structs[n] for n in (
+    'wc_conv_seg', 'wc_conv_args', 'wc_gnb_epi', 'wc_wgrad_args', 'wc_wino_pack_job', 'wc_bsum_job'))
+MAX_TAPS, OK, E_SHAPE, E_ARG = (ABI.constants[n] for n in ('WC_MAX_TAPS', 'WC_OK', 'WC_E_SHAPE', 'WC_E_ARG'))
+NOISE_NONE, NOISE_TENSOR, NOISE_PHILOX = (ABI.constants['WC_NOISE_' + n] for n in ('NONE', 'TENSOR', 'PHILOX'))
+ACT_NONE, ACT_GELU, ACT_SILU, ACT_PRELU, ACT_TANH01 = (ABI.constants['WC_ACT_' + n] for n in (
+    'NONE', 'GELU', 'SILU', 'PRELU', 'TANH01'))
 
 _libs = {}
 _active = threading.local()
@@ -198,6 +59,13 @@ def active_variant() -> str:
     return getattr(_active, 'v', '')
 
 
+def _bind(lib, name: str):
+    """Give lib.<name> the argument and return types the header declares for it."""
+    fn = getattr(lib, name)
+    fn.restype, fn.argtypes = ABI.functions[name]
+    return fn
+
+
 def load(build_if_missing: bool = True):
     """Open the kernel library of the active variant (building it first if it is absent and hipcc
     exists)."""
@@ -215,18 +83,10 @@ def load(build_if_missing: bool = True):
     verify_source_hash(lib, v)
     forms.announce()  # a run with non-default kernel forms says so before its first native call
     stale_ok = os.environ.get('WC_ALLOW_STALE_LIB', '0') == '1'
-    for name, argtypes in _SIGS.items():
+    for name in ABI.functions:
         if stale_ok and not hasattr(lib, name):  # an older A/B build may lack newer entry points
             continue
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
-    if hasattr(lib, 'wc_small_wgrad_workspace'):
-        lib.wc_small_wgrad_workspace.restype = ctypes.c_int64
-    lib.wc_version.argtypes = []
-    lib.wc_version.restype = ctypes.c_char_p
-    lib.wc_last_kernel_name.argtypes = []
-    lib.wc_last_kernel_name.restype = ctypes.c_char_p
+        _bind(lib, name)
     for name, value in _selectors.items():  # kernel-form selectors set before this variant was opened
         if hasattr(lib, name) or not stale_ok:
             getattr(lib, name)(value)
@@ -246,9 +106,7 @@ def verify_source_hash(lib, variant: str = ''):
         if stale_ok:  # an older A/B build from before the digest existed
             return None
         raise RuntimeError('weatherconverter_amd: kernel library has no wc_source_hash (built from other sources)')
-    lib.wc_source_hash.argtypes = []
-    lib.wc_source_hash.restype = ctypes.c_char_p
-    got = lib.wc_source_hash().decode()
+    got = _bind(lib, 'wc_source_hash')().decode()
     want = _build.source_hash(_VARIANT_FLAG.get(variant, ''))
     if got != want and not stale_ok:
         raise RuntimeError(f'weatherconverter_amd: kernel library {variant or "default"} was built from other sources '
@@ -279,7 +137,7 @@ def set_selector(name: str, value: int, valid=lambda prev: True) -> int:
 
 def check(status: int, op: str):
     if status != 0:
-        kind = {-1: 'unsupported shape', -2: 'bad argument'}.get(status, f'hipError {status}')
+        kind = {E_SHAPE: 'unsupported shape', E_ARG: 'bad argument'}.get(status, f'hipError {status}')
         raise RuntimeError(f'weatherconverter_amd kernel {op} failed: {kind}')
 
 

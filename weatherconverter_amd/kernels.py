@@ -198,6 +198,24 @@ class GnPart:
         return getattr(v.t, '_wc_gn', None) is self and v.c0 % 32 == 0 and v.C % 32 == 0
 
 
+def _fill_seg(cs: ConvSeg, s: Seg, B: int):
+    """One K segment (wc_conv_seg) of a conv's or a weight gradient's arguments."""
+    v = s.view
+    v.check()
+    _req(v.B == B, 'segment batch mismatch')
+    _req(len(s.taps) <= _native.MAX_TAPS, 'too many taps')
+    cs.src, cs.C, cs.ldc, cs.H, cs.W = v.ptr, v.C, v.ldc, v.H, v.W
+    cs.sy = cs.sx = s.stride
+    cs.ntaps = len(s.taps)
+    for j, (dy, dx) in enumerate(s.taps):
+        cs.dy[j], cs.dx[j] = dy, dx
+    if s.scale is not None:
+        _req(s.scale.shape == (B, v.C) and s.shift.shape == (B, v.C), 'GN affine shape')
+        cs.scale, cs.shift = s.scale.data_ptr(), s.shift.data_ptr()
+    cs.silu = int(s.silu)
+    cs.kbase = s.kbase
+
+
 def _conv_args(segs: Sequence[Seg], N: int, bias: Optional[torch.Tensor], out: Optional[View], Hm: int, Wm: int,
                temb: Optional[torch.Tensor], temb_ld: int, res: Optional[View], out_map,
                out_nchw: Optional[torch.Tensor], act: int, absmax: Optional[torch.Tensor] = None,
@@ -207,27 +225,7 @@ def _conv_args(segs: Sequence[Seg], N: int, bias: Optional[torch.Tensor], out: O
     _req(1 <= len(segs) <= 2, 'conv takes 1 or 2 K segments')
     B = segs[0].view.B
     for i, s in enumerate(segs):
-        v = s.view
-        v.check()
-        _req(v.B == B, 'segment batch mismatch')
-        _req(len(s.taps) <= _native.MAX_TAPS, 'too many taps')
-        cs = a.seg[i]
-        cs.src = v.ptr
-        cs.C = v.C
-        cs.ldc = v.ldc
-        cs.H = v.H
-        cs.W = v.W
-        cs.sy = cs.sx = s.stride
-        cs.ntaps = len(s.taps)
-        for j, (dy, dx) in enumerate(s.taps):
-            cs.dy[j] = dy
-            cs.dx[j] = dx
-        if s.scale is not None:
-            _req(s.scale.shape == (B, v.C) and s.shift.shape == (B, v.C), 'GN affine shape')
-            cs.scale = s.scale.data_ptr()
-            cs.shift = s.shift.data_ptr()
-        cs.silu = int(s.silu)
-        cs.kbase = s.kbase
+        _fill_seg(a.seg[i], s, B)
     a.nseg = len(segs)
     a.B, a.Hm, a.Wm, a.N = B, Hm, Wm, N
     a.bias = _ptr(bias)
@@ -599,6 +597,28 @@ def pack_wino_raw(w4: torch.Tensor, wres: Optional[torch.Tensor] = None, transpo
     return X6Weight(data, N, BN, C0, C1, 'wino', wsinv, bool(C1))
 
 
+def _job_table(rows: List[List[int]], job, dev):
+    """The rows (one `job` struct each, as int64 words) as a device tensor, which the caller holds until it
+    has launched, and that tensor's address as the `job` pointer the batch entry points take.  Rows stay
+    plain integers: this is on the training step's host path."""
+    tab = torch.empty((len(rows), ctypes.sizeof(job) // 8), dtype=torch.int64, pin_memory=True)
+    tab.copy_(torch.tensor(rows, dtype=torch.int64))
+    dtab = tab.to(dev, non_blocking=True)
+    return dtab, ctypes.cast(dtab.data_ptr(), ctypes.POINTER(job))
+
+
+def wino_pack_job_row(w: int, wres: int, out: int, wsinv: int, N: int, C0: int, C1: int, transposed: int, BN: int,
+                      wg0: int) -> List[int]:
+    """One wc_wino_pack_job as int64 words: the four pointers, then its ints two to a word (the first in
+    the low half), pad0 / pad1 zero."""
+    return [w, wres, out, wsinv, N | (C0 << 32), C1 | (transposed << 32), BN | (wg0 << 32), 0]
+
+
+def bsum_job_row(sums: int, out: int, C: int, idx: int, accumulate: int) -> List[int]:
+    """One wc_bsum_job as int64 words (as wino_pack_job_row), pad zero."""
+    return [sums, out, C | (idx << 32), accumulate]
+
+
 def pack_wino_raw_batch(reqs: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], bool]]) -> List[X6Weight]:
     """pack_wino_raw of every (w4, wres, transposed) in reqs in ONE launch (wc_pack_wino_batch): the same
     pieces and scales, bit for bit, as one wc_pack_wino_raw each."""
@@ -622,15 +642,13 @@ def pack_wino_raw_batch(reqs: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor
         data = torch.empty((Np // BN, (12 * C0 + C1) // 16 * 2 * 2 * BN * 8), dtype=torch.int16, device=dev)
         wsinv = torch.empty(Np, dtype=torch.float32, device=dev)
         outs.append(X6Weight(data, N, BN, C0, C1, 'wino', wsinv, bool(C1)))
-        rows.append([w4.data_ptr(), _ptr(wres) or 0, data.data_ptr(), wsinv.data_ptr(),
-                     N | (C0 << 32), C1 | (int(transposed) << 32), BN | (wg << 32), 0])
+        rows.append(wino_pack_job_row(w4.data_ptr(), _ptr(wres) or 0, data.data_ptr(), wsinv.data_ptr(), N, C0, C1,
+                                      int(transposed), BN, wg))
         wg += Np
         max_c0 = max(max_c0, C0)
     _req(wg < 2**31, 'pack batch too large')
-    tab = torch.empty((len(rows), 8), dtype=torch.int64, pin_memory=True)
-    tab.copy_(torch.tensor(rows, dtype=torch.int64))
-    dtab = tab.to(dev, non_blocking=True)
-    _timed('pack_wino_batch_kernel', 'wc_pack_wino_batch', 0.0, dtab.data_ptr(), len(rows), wg, max_c0, _stream())
+    dtab, jobs = _job_table(rows, _native.WinoPackJob, dev)
+    _timed('pack_wino_batch_kernel', 'wc_pack_wino_batch', 0.0, jobs, len(rows), wg, max_c0, _stream())
     return outs
 
 
@@ -1398,23 +1416,6 @@ def noise_embed(noise: torch.Tensor, ang: torch.Tensor, out: View):
 
 # ---- UNet backward (csrc/wc_backward.hip, csrc/wc_attention_bwd.hip) ----
 
-def _fill_seg(cs, s: Seg, B: int):
-    v = s.view
-    v.check()
-    _req(v.B == B, 'segment batch mismatch')
-    _req(len(s.taps) <= _native.MAX_TAPS, 'too many taps')
-    cs.src, cs.C, cs.ldc, cs.H, cs.W = v.ptr, v.C, v.ldc, v.H, v.W
-    cs.sy = cs.sx = s.stride
-    cs.ntaps = len(s.taps)
-    for j, (dy, dx) in enumerate(s.taps):
-        cs.dy[j], cs.dx[j] = dy, dx
-    if s.scale is not None:
-        _req(s.scale.shape == (B, v.C) and s.shift.shape == (B, v.C), 'GN affine shape')
-        cs.scale, cs.shift = s.scale.data_ptr(), s.shift.data_ptr()
-    cs.silu = int(s.silu)
-    cs.kbase = s.kbase
-
-
 def absmax_images(v: View) -> torch.Tensor:
     """float32[B]: max |x| over each image of the view (wc_absmax_images)."""
     v.check()
@@ -1606,11 +1607,9 @@ def bsum_flush():
     B = q[0][0].shape[0]
     s = _stream()
     for jobs in launches:
-        tab = torch.empty((len(jobs), 4), dtype=torch.int64, pin_memory=True)
-        rows = [[sm.data_ptr(), o.data_ptr(), sm.shape[1] | (idx << 32), int(acc)] for sm, idx, o, acc in jobs]
-        tab.copy_(torch.tensor(rows, dtype=torch.int64))
-        dtab = tab.to(q[0][2].device, non_blocking=True)
-        _native.call('wc_bsum_batch', dtab.data_ptr(), len(jobs), B, max(sm.shape[1] for sm, _, _, _ in jobs), s)
+        rows = [bsum_job_row(sm.data_ptr(), o.data_ptr(), sm.shape[1], idx, int(acc)) for sm, idx, o, acc in jobs]
+        dtab, table = _job_table(rows, _native.BsumJob, q[0][2].device)
+        _native.call('wc_bsum_batch', table, len(jobs), B, max(sm.shape[1] for sm, _, _, _ in jobs), s)
 
 
 def gn_backward(dz: View, x: View, sc0: torch.Tensor, sh0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
