@@ -10,6 +10,7 @@ import argparse
 import os
 import statistics
 import sys
+from dataclasses import replace
 
 import torch
 
@@ -18,8 +19,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def no_f3_resample(eng):
     """Down-sampling / transposed convs back on bf16x6 (no producer-bound f16x3)."""
-    eng.down_convs = [None if d is None else (d[0], d[1], d[2], None) for d in eng.down_convs]
-    eng.up_convs = [None if u is None else ([(t, w, w6, None) for t, w, w6, _ in u[0]], u[1]) for u in eng.up_convs]
+    eng.down_convs = [None if d is None else replace(d, f3=None, f3s=None) for d in eng.down_convs]
+    eng.up_convs = [None if u is None else replace(u, f3t=None, parts=[(t, replace(p, f3=None)) for t, p in u.parts])
+                    for u in eng.up_convs]
 
 
 def no_gn_partials(eng):

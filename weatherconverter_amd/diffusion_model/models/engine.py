@@ -52,9 +52,8 @@ import torch
 
 from ... import forms
 from ... import kernels as K
-from ...kernels import Seg, View
+from ...kernels import TAPS3, Seg, View
 
-TAPS3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
 TAPS1 = [(0, 0)]
 TAPS4S2 = [(ky - 1, kx - 1) for ky in range(4) for kx in range(4)]
 # ConvTranspose2d(4, stride 2, pad 1): output row 2m+p gathers input rows m+dy with kernel row ky.
@@ -78,26 +77,40 @@ def pack_convT(wt: torch.Tensor, py: int, px: int) -> Tuple[List[Tuple[int, int]
 
 
 @dataclass
+class ConvPack:
+    """One conv as the engine can launch it: the bias and every packed form of the weight, each field
+    named for the entry point it feeds.  A form the conv was not packed for is None."""
+    w: torch.Tensor  # fp32 [N][K] (pack_conv): wc_conv_igemm
+    b: torch.Tensor
+    x6: Optional[K.X6Weight] = None  # bf16x6, natural K order: wc_conv_igemm_x6
+    x6h: Optional[K.X6Weight] = None  # bf16x6, halo order: wc_conv3x3_x6
+    f3: Optional[K.X6Weight] = None  # f16x3, natural K order: wc_conv_igemm_f16x3, wc_proj_f16x3(_qkv)
+    f3h: Optional[K.X6Weight] = None  # f16x3, halo order: wc_conv3x3_f16x3
+    wn: Optional[K.X6Weight] = None  # Winograd F(2,3): wc_conv3x3_wino_f16x3 (forms.wino)
+    f3s: Optional[K.X6Weight] = None  # f16x3, space-to-depth: wc_conv4x4s2_f16x3 (forms.down_s2d)
+    gb: Tuple[float, float] = (0.0, 0.0)  # (max|gamma|, max|beta|) of the GroupNorm in front (f16x3 bound)
+
+
+@dataclass
+class UpPack:
+    """A 4x4 / stride-2 ConvTranspose: one launch of wc_convtr4x4s2_f16x3 (f3t, forms.up_ct), or its
+    four output parities as implicit-GEMM convs, (taps, pack) for (py, px) = (0, 0), (0, 1), (1, 0), (1, 1)."""
+    b: torch.Tensor
+    f3t: Optional[K.X6Weight]
+    parts: List[Tuple[List[Tuple[int, int]], ConvPack]]
+
+
+@dataclass
 class ResPack:
     ci: int
     co: int
     g1: torch.Tensor
     be1: torch.Tensor
-    w1: torch.Tensor
-    b1: torch.Tensor
     g2: torch.Tensor
     be2: torch.Tensor
-    w2: torch.Tensor  # conv2 (9*co) ++ residual 1x1 (ci)
-    b2: torch.Tensor
     temb_off: int
-    w1x6: Optional[Tuple[Optional[K.X6Weight], K.X6Weight]] = None  # bf16x6 re-packs (halo, natural order)
-    w2x6: Optional[Tuple[Optional[K.X6Weight], K.X6Weight]] = None
-    w1f3: Optional[K.X6Weight] = None  # f16x3 re-packs (precision 'f16x3')
-    w2f3: Optional[K.X6Weight] = None
-    gb1: Tuple[float, float] = (0.0, 0.0)  # (max|gamma|, max|beta|) of the GroupNorms (f16x3 bound)
-    gb2: Tuple[float, float] = (0.0, 0.0)
-    w1wn: Optional[K.X6Weight] = None  # Winograd F(2,3) packs (precision 'f16x3', forms.wino)
-    w2wn: Optional[K.X6Weight] = None
+    conv1: ConvPack
+    conv2: ConvPack  # weight: conv2 (9*co) ++ residual 1x1 (ci); bias: the sum of the two
 
 
 @dataclass
@@ -106,14 +119,8 @@ class AttnPack:
     heads: int
     g: torch.Tensor
     be: torch.Tensor
-    w_in: torch.Tensor
-    b_in: torch.Tensor
-    w_out: torch.Tensor
-    b_out: torch.Tensor
-    w_in_x6: Optional[K.X6Weight] = None
-    w_out_x6: Optional[K.X6Weight] = None
-    w_in_f3: Optional[K.X6Weight] = None  # f16x3 re-packs (in_proj: GN bound, out_proj: V bound)
-    w_out_f3: Optional[K.X6Weight] = None
+    proj_in: ConvPack  # f16x3 under the GN bound
+    proj_out: ConvPack  # f16x3 under the V bound
     qkv_l1: Optional[torch.Tensor] = None  # f16x3: host row-L1 norms of W_in and |b_in| (bounds)
     qkv_babs: Optional[torch.Tensor] = None
     gb: Tuple[float, float] = (0.0, 0.0)
@@ -207,7 +214,6 @@ class UnetEngine:
 
     def _pack(self):
         m = self.model
-        self.res_packs = []
         self.temb_rows_w, self.temb_rows_b = [], []
         self._temb_P = 0
         with torch.no_grad():
@@ -215,11 +221,11 @@ class UnetEngine:
             self.down_convs = []
             for blk in m.downs:
                 if blk.down_sample:
-                    w = pack_conv(blk.down_sample_conv.weight)
-                    ci = blk.down_sample_conv.in_channels
-                    self.down_convs.append((w, blk.down_sample_conv.bias.detach().float(),
-                                            self._x6(w, ci, len(TAPS4S2)), self._f3n(w, ci, len(TAPS4S2)),
-                                            self._f3s(w, ci)))
+                    dn = blk.down_sample_conv
+                    p = self._pack_resample(pack_conv(dn.weight), dn.bias.detach().float(), dn.in_channels,
+                                            len(TAPS4S2))
+                    p.f3s = self._f3s(p.w, dn.in_channels)
+                    self.down_convs.append(p)
                 else:
                     self.down_convs.append(None)
             self.mids = [self._pack_stage(blk, n_res=blk.num_layers + 1, attn=True) for blk in m.mids]
@@ -227,23 +233,21 @@ class UnetEngine:
             self.up_convs = []
             for blk in m.ups:
                 if blk.up_sample:
-                    ci = blk.up_sample_conv.in_channels
-                    parts = [pack_convT(blk.up_sample_conv.weight, py, px) for py in (0, 1) for px in (0, 1)]
-                    parts = [(taps, w, self._x6(w, ci, len(taps)), self._f3n(w, ci, len(taps))) for taps, w in parts]
-                    self.up_convs.append((parts, blk.up_sample_conv.bias.detach().float(),
-                                          self._f3t(blk.up_sample_conv.weight, ci)))
+                    up = blk.up_sample_conv
+                    b = up.bias.detach().float()
+                    parts = [pack_convT(up.weight, py, px) for py in (0, 1) for px in (0, 1)]
+                    parts = [(taps, self._pack_resample(w, b, up.in_channels, len(taps))) for taps, w in parts]
+                    self.up_convs.append(UpPack(b, self._f3t(up.weight, up.in_channels), parts))
                 else:
                     self.up_convs.append(None)
             self.conv_in_w = m.conv_in.weight.detach().float().contiguous()
             self.conv_in_b = m.conv_in.bias.detach().float().contiguous()
             self.norm_out = (m.norm_out.weight.detach().float(), m.norm_out.bias.detach().float())
-            self.conv_out_w = pack_conv(m.conv_out.weight)
-            self.conv_out_x6 = self._x6(self.conv_out_w, m.conv_out.in_channels, 9)
-            self.conv_out_f3 = None
+            co = self.conv_out = ConvPack(pack_conv(m.conv_out.weight), m.conv_out.bias.detach().float().contiguous())
+            co.x6 = self._x6(co.w, m.conv_out.in_channels, 9)
             if self.precision == 'f16x3' and m.conv_out.in_channels % 16 == 0:
-                self.conv_out_f3 = K.pack_f16x3(self.conv_out_w, m.conv_out.in_channels, order='natural')
-                self.norm_out_gb = (float(m.norm_out.weight.abs().max()), float(m.norm_out.bias.abs().max()))
-            self.conv_out_b = m.conv_out.bias.detach().float().contiguous()
+                co.f3 = K.pack_f16x3(co.w, m.conv_out.in_channels, order='natural')
+                co.gb = (float(m.norm_out.weight.abs().max()), float(m.norm_out.bias.abs().max()))
             # <= 4 output channels: the dedicated HBM-bound head kernel (an MFMA tile would waste 20x)
             self.conv_out_head = None
             if m.conv_out.out_channels <= 4 and m.conv_out.in_channels % 16 == 0:
@@ -259,24 +263,27 @@ class UnetEngine:
         tl = blk.t_emb_layers[i][1]
         ci, co = f[2].in_channels, f[2].out_channels
         w2 = torch.cat([pack_conv(s[2].weight), r.weight.detach().reshape(co, ci).float()], 1).contiguous()
+        c1 = ConvPack(pack_conv(f[2].weight), f[2].bias.detach().float().contiguous())
+        c2 = ConvPack(w2, (s[2].bias.detach().float() + r.bias.detach().float()).contiguous())
         p = ResPack(ci=ci, co=co, g1=f[0].weight.detach().float(), be1=f[0].bias.detach().float(),
-                    w1=pack_conv(f[2].weight), b1=f[2].bias.detach().float().contiguous(),
-                    g2=s[0].weight.detach().float(), be2=s[0].bias.detach().float(), w2=w2,
-                    b2=(s[2].bias.detach().float() + r.bias.detach().float()).contiguous(), temb_off=self._temb_P)
+                    g2=s[0].weight.detach().float(), be2=s[0].bias.detach().float(), temb_off=self._temb_P,
+                    conv1=c1, conv2=c2)
         if self.precision in ('bf16x6', 'f16x3') and ci % 16 == 0 and co % 16 == 0:
             # halo-order pack for the 3x3 kernel (bf16x6 mode), natural-order pack for the
             # implicit-GEMM fallback (grids the halo kernel does not tile), f16x3 pack
             f3 = self.precision == 'f16x3'
-            p.w1x6 = (None if f3 else K.pack_x6(p.w1, ci), self._x6(p.w1, ci, 9))
-            p.w2x6 = (None if f3 else K.pack_x6(p.w2, co, ci), self._x6(p.w2, co, 9, ci))
+            c1.x6h = None if f3 else K.pack_x6(c1.w, ci)
+            c1.x6 = self._x6(c1.w, ci, 9)
+            c2.x6h = None if f3 else K.pack_x6(c2.w, co, ci)
+            c2.x6 = self._x6(c2.w, co, 9, ci)
             if f3:
-                p.w1f3 = K.pack_f16x3(p.w1, ci)
-                p.w2f3 = K.pack_f16x3(p.w2, co, ci, res_f16=True)  # residual bounded by GN1's stats of X
+                c1.f3h = K.pack_f16x3(c1.w, ci)
+                c2.f3h = K.pack_f16x3(c2.w, co, ci, res_f16=True)  # residual bounded by GN1's stats of X
                 if forms.current().wino:
-                    p.w1wn = K.pack_wino(p.w1, ci)
-                    p.w2wn = K.pack_wino(p.w2, co, ci)
-                p.gb1 = (float(p.g1.abs().max()), float(p.be1.abs().max()))
-                p.gb2 = (float(p.g2.abs().max()), float(p.be2.abs().max()))
+                    c1.wn = K.pack_wino(c1.w, ci)
+                    c2.wn = K.pack_wino(c2.w, co, ci)
+                c1.gb = (float(p.g1.abs().max()), float(p.be1.abs().max()))
+                c2.gb = (float(p.g2.abs().max()), float(p.be2.abs().max()))
         self.temb_rows_w.append(tl.weight.detach().float())
         self.temb_rows_b.append(tl.bias.detach().float())
         self._temb_P += co
@@ -288,12 +295,13 @@ class UnetEngine:
             return None
         return K.pack_x6(w, c0, c1, ntaps=ntaps, order='natural')
 
-    def _f3n(self, w: torch.Tensor, c0: int, ntaps: int) -> Optional[K.X6Weight]:
-        """f16x3 (natural K order) pack for a resampling conv whose input range comes from its
-        producer's per-image absmax, or None outside f16x3 mode."""
-        if self.precision != 'f16x3' or c0 % 16:
-            return None
-        return K.pack_f16x3(w, c0, ntaps=ntaps, order='natural')
+    def _pack_resample(self, w: torch.Tensor, b: torch.Tensor, c0: int, ntaps: int) -> ConvPack:
+        """A resampling conv (the down conv, one ConvT parity): bf16x6 outside fp32 mode; in f16x3 mode
+        also the f16x3 pack, for an input whose range comes from its producer's per-image absmax."""
+        p = ConvPack(w, b, x6=self._x6(w, c0, ntaps))
+        if self.precision == 'f16x3' and c0 % 16 == 0:
+            p.f3 = K.pack_f16x3(w, c0, ntaps=ntaps, order='natural')
+        return p
 
     def _f3s(self, w: torch.Tensor, c0: int) -> Optional[K.X6Weight]:
         """f16x3 space-to-depth pack of a 4x4 / stride-2 down conv for wc_conv4x4s2_f16x3 (the halo
@@ -314,18 +322,19 @@ class UnetEngine:
     def _pack_attn(self, blk, i: int) -> AttnPack:
         mha, gn = blk.attentions[i], blk.attention_norms[i]
         c = mha.embed_dim
+        pi = ConvPack(mha.in_proj_weight.detach().float().contiguous(),
+                      mha.in_proj_bias.detach().float().contiguous())
+        po = ConvPack(mha.out_proj.weight.detach().float().contiguous(),
+                      mha.out_proj.bias.detach().float().contiguous())
         p = AttnPack(c=c, heads=mha.num_heads, g=gn.weight.detach().float(), be=gn.bias.detach().float(),
-                     w_in=mha.in_proj_weight.detach().float().contiguous(),
-                     b_in=mha.in_proj_bias.detach().float().contiguous(),
-                     w_out=mha.out_proj.weight.detach().float().contiguous(),
-                     b_out=mha.out_proj.bias.detach().float().contiguous())
-        p.w_in_x6 = self._x6(p.w_in, c, 1)
-        p.w_out_x6 = self._x6(p.w_out, c, 1)
+                     proj_in=pi, proj_out=po)
+        pi.x6 = self._x6(pi.w, c, 1)
+        po.x6 = self._x6(po.w, c, 1)
         if self.precision == 'f16x3':
-            p.w_in_f3 = K.pack_f16x3(p.w_in, c, ntaps=1, order='natural')
-            p.w_out_f3 = K.pack_f16x3(p.w_out, c, ntaps=1, order='natural')
-            p.qkv_l1 = p.w_in.double().abs().sum(1).cpu()
-            p.qkv_babs = p.b_in.double().abs().cpu()
+            pi.f3 = K.pack_f16x3(pi.w, c, ntaps=1, order='natural')
+            po.f3 = K.pack_f16x3(po.w, c, ntaps=1, order='natural')
+            p.qkv_l1 = pi.w.double().abs().sum(1).cpu()
+            p.qkv_babs = pi.b.double().abs().cpu()
             p.gb = (float(p.g.abs().max()), float(p.be.abs().max()))
         return p
 
@@ -367,92 +376,85 @@ class UnetEngine:
         if gp is not None and not fused:
             K.gn_partials(v, gp)
 
-    def conv(self, segs, w: torch.Tensor, w6: Optional[K.X6Weight], bias, out: Optional[View], H: int, W: int,
-             absmax: Optional[torch.Tensor] = None, gn_p64: int = 0, gn_defer: bool = False, **kw) -> Tuple[bool, bool]:
+    def conv(self, segs, p: ConvPack, out: Optional[View], H: int, W: int, absmax: Optional[torch.Tensor] = None,
+             gn_p64: int = 0, gn_defer: bool = False, **kw) -> Tuple[bool, bool]:
         """Any conv: bf16x6 implicit GEMM when packed for it, else fp32 MFMA.  Returns (the per-image
         output absmax was emitted into `absmax`, the output's GN partials came from the epilogue);
         partials not emitted are filled by a stats pass unless gn_defer."""
-        gp = K.GnPart.of(out)
-        fused = False
-        if w6 is not None:
-            fused = K.gn_conv_ok(out, gp, w6.N, H, W, 256 if w6.N <= 64 else 128)
-            K.conv_igemm_x6(segs, w6, bias, out, Hm=H, Wm=W, absmax=absmax, gn=gp if fused else None, gn_p64=gn_p64,
-                            **kw)
+        gp = None
+        if p.x6 is not None:
+            gp = K.gn_epilogue(out, p.x6.N, H, W, K.igemm_bm(p.x6.N))
+            K.conv_igemm_x6(segs, p.x6, p.b, out, Hm=H, Wm=W, absmax=absmax, gn=gp, gn_p64=gn_p64, **kw)
         else:
-            K.conv_igemm(segs, w, bias, out, Hm=H, Wm=W, **kw)
+            K.conv_igemm(segs, p.w, p.b, out, Hm=H, Wm=W, **kw)
         if not gn_defer:
-            self._gn_fill(out, fused)
-        return absmax is not None and w6 is not None, fused
+            self._gn_fill(out, gp is not None)
+        return absmax is not None and p.x6 is not None, gp is not None
 
-    def resample(self, segs, pack, bias, out: View, H: int, W: int, bound: Optional[torch.Tensor], gn_p64: int = 0,
+    def resample(self, segs, p: ConvPack, out: View, H: int, W: int, bound: Optional[torch.Tensor], gn_p64: int = 0,
                  gn_defer: bool = False, **kw) -> bool:
         """Down-sampling conv / one transposed-conv parity: f16x3 implicit GEMM scaled per image by
         the producer's absmax when there is one (and the tiles stay within an image), else bf16x6.
         Returns whether the output's GN partials came from the epilogue."""
-        w, w6, w3 = pack
-        if w3 is not None and bound is not None and (H * W) % (256 if w3.N <= 64 else 128) == 0:
-            gp = K.GnPart.of(out)
-            fused = K.gn_conv_ok(out, gp, w3.N, H, W, 256 if w3.N <= 64 else 128)
-            K.conv_igemm_f16x3(segs, w3, bias, out, Hm=H, Wm=W, a_exp=60, a_bound=bound, gn=gp if fused else None,
-                               gn_p64=gn_p64, **kw)
+        if p.f3 is not None and bound is not None and (H * W) % K.igemm_bm(p.f3.N) == 0:
+            gp = K.gn_epilogue(out, p.f3.N, H, W, K.igemm_bm(p.f3.N))
+            K.conv_igemm_f16x3(segs, p.f3, p.b, out, Hm=H, Wm=W, a_exp=60, a_bound=bound, gn=gp, gn_p64=gn_p64, **kw)
             if not gn_defer:
-                self._gn_fill(out, fused)
-            return fused
-        return self.conv(segs, w, w6, bias, out, H, W, gn_p64=gn_p64, gn_defer=gn_defer, **kw)[1]
+                self._gn_fill(out, gp is not None)
+            return gp is not None
+        return self.conv(segs, p, out, H, W, gn_p64=gn_p64, gn_defer=gn_defer, **kw)[1]
 
-    def conv3(self, segs, w: torch.Tensor, w6, w3: Optional[K.X6Weight], gb: Tuple[float, float], bias, out: View,
-              H: int, W: int, a_bound: Optional[torch.Tensor] = None, absmax: Optional[torch.Tensor] = None,
-              wn: Optional[K.X6Weight] = None, **kw) -> bool:
+    def conv3(self, segs, p: ConvPack, out: View, H: int, W: int, a_bound: Optional[torch.Tensor] = None,
+              absmax: Optional[torch.Tensor] = None, **kw) -> bool:
         """A ResBlock 3x3 stride-1 conv (GN+SiLU prologue): the halo-tiled kernel in f16x3 (bound
-        from the GroupNorm affine gb and the group size) or bf16x6 when the grid tiles, else the
+        from the GroupNorm affine p.gb and the group size) or bf16x6 when the grid tiles, else the
         bf16x6 implicit GEMM (or fp32 MFMA in fp32 mode).  GN partials of `out` are emitted by the
         split-precision epilogues where they can be, else filled by a stats pass.  Returns whether
         the absmax was emitted."""
-        gp = K.GnPart.of(out)
-        if (wn is not None and K.wino_eligible(segs, wn.N, H, W) and (len(segs) == 1 or a_bound is not None)
-                and (w3 is None or K.x6_eligible(segs, w3.N, H, W))):
+        if (p.wn is not None and K.wino_eligible(segs, p.wn.N, H, W) and (len(segs) == 1 or a_bound is not None)
+                and (p.f3h is None or K.x6_eligible(segs, p.f3h.N, H, W))):
             # the Winograd F(2,3)-along-x form of the same f16x3 conv (1.5x fewer MFMAs)
             n_group = H * W * segs[0].view.C // 8
-            fused = K.gn_conv_ok(out, gp, wn.N, H, W)
-            K.conv3x3_wino(segs, wn, bias, out, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(gb[0], gb[1], n_group),
-                           a_bound=a_bound, absmax=absmax, gn=gp if fused else None, **kw)
-            self._gn_fill(out, fused)
+            gp = K.gn_epilogue(out, p.wn.N, H, W)
+            K.conv3x3_wino(segs, p.wn, p.b, out, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(p.gb[0], p.gb[1], n_group),
+                           a_bound=a_bound, absmax=absmax, gn=gp, **kw)
+            self._gn_fill(out, gp is not None)
             return absmax is not None
-        if w3 is not None and K.x6_eligible(segs, w3.N, H, W):
+        if p.f3h is not None and K.x6_eligible(segs, p.f3h.N, H, W):
             n_group = H * W * segs[0].view.C // 8
-            fused = K.gn_conv_ok(out, gp, w3.N, H, W)
-            K.conv3x3_f16x3(segs, w3, bias, out, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(gb[0], gb[1], n_group),
-                            a_bound=a_bound if w3.res_f16 else None, absmax=absmax, gn=gp if fused else None, **kw)
-            self._gn_fill(out, fused)
+            gp = K.gn_epilogue(out, p.f3h.N, H, W)
+            K.conv3x3_f16x3(segs, p.f3h, p.b, out, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(p.gb[0], p.gb[1], n_group),
+                            a_bound=a_bound if p.f3h.res_f16 else None, absmax=absmax, gn=gp, **kw)
+            self._gn_fill(out, gp is not None)
             return absmax is not None
-        if w6 is not None and w6[0] is not None and K.x6_eligible(segs, w6[0].N, H, W):
-            fused = K.gn_conv_ok(out, gp, w6[0].N, H, W)
-            K.conv3x3_x6(segs, w6[0], bias, out, Hm=H, Wm=W, absmax=absmax, gn=gp if fused else None, **kw)
-            self._gn_fill(out, fused)
+        if p.x6h is not None and K.x6_eligible(segs, p.x6h.N, H, W):
+            gp = K.gn_epilogue(out, p.x6h.N, H, W)
+            K.conv3x3_x6(segs, p.x6h, p.b, out, Hm=H, Wm=W, absmax=absmax, gn=gp, **kw)
+            self._gn_fill(out, gp is not None)
             return absmax is not None
-        return self.conv(segs, w, None if w6 is None else w6[1], bias, out, H, W, absmax=absmax, **kw)[0]
+        return self.conv(segs, p, out, H, W, absmax=absmax, **kw)[0]
 
     def resblock(self, X: View, Y: View, p: ResPack, temb: torch.Tensor, temb_ld: int,
                  absmax: Optional[torch.Tensor] = None) -> bool:
         B, H, W = X.B, X.H, X.W
         xb = None
-        if p.w2f3 is not None and p.w2f3.res_f16:
+        if p.conv2.f3h is not None and p.conv2.f3h.res_f16:
             sc1, sh1, xb = self._gn(X, p.g1, p.be1, bound=True)  # xb bounds |X| (conv2's residual input)
         else:
             sc1, sh1 = self._gn(X, p.g1, p.be1)
         h = View.full(self._new(B, H, W, p.co, gn_sw=self._sw(p.co)))
-        self.conv3([Seg(X, TAPS3, scale=sc1, shift=sh1, silu=True)], p.w1, p.w1x6, p.w1f3, p.gb1, p.b1, h, H, W,
-                   temb=temb[:, p.temb_off:], temb_ld=temb_ld, wn=p.w1wn)
+        self.conv3([Seg(X, TAPS3, scale=sc1, shift=sh1, silu=True)], p.conv1, h, H, W, temb=temb[:, p.temb_off:],
+                   temb_ld=temb_ld)
         sc2, sh2 = self._gn(h, p.g2, p.be2)
-        return self.conv3([Seg(h, TAPS3, scale=sc2, shift=sh2, silu=True),
-                           Seg(X, TAPS1, kbase=9 * p.co)], p.w2, p.w2x6, p.w2f3, p.gb2, p.b2, Y, H, W, a_bound=xb,
-                          absmax=absmax, wn=p.w2wn)
+        return self.conv3([Seg(h, TAPS3, scale=sc2, shift=sh2, silu=True), Seg(X, TAPS1, kbase=9 * p.co)], p.conv2, Y,
+                          H, W, a_bound=xb, absmax=absmax)
 
     def attention(self, Y: View, p: AttnPack, absmax: Optional[torch.Tensor] = None) -> bool:
         B, H, W, C = Y.B, Y.H, Y.W, Y.C
         N = H * W
         sc, sh = self._gn(Y, p.g, p.be)
-        if p.w_in_f3 is not None:
+        pi, po = p.proj_in, p.proj_out
+        if pi.f3 is not None:
             # in_proj: GN output bound; attention: q/k/v bounds; out_proj: |O| <= max|V| (convex
             # combination of V rows), so the V exponent bounds it
             a_exp = K.f16x3_a_exp(p.gb[0], p.gb[1], N * C // 8)
@@ -466,41 +468,38 @@ class UnetEngine:
                     # GN applied and split once per element (not once per 128-column N tile), then
                     # both GEMM operands staged by LDS-DMA
                     a3 = K.split_f16x3_tiled(Y, a_exp, sc, sh)
-                    K.proj_f16x3_qkv(Y, a3, p.w_in_f3, p.b_in, qkv3, a_exp=a_exp, C=C, heads=p.heads, exps=exps)
+                    K.proj_f16x3_qkv(Y, a3, pi.f3, pi.b, qkv3, a_exp=a_exp, C=C, heads=p.heads, exps=exps)
                     del a3
                 else:
-                    K.conv_igemm_f16x3_qkv(seg, p.w_in_f3, p.b_in, qkv3, Hm=H, Wm=W, a_exp=a_exp, C=C,
-                                           heads=p.heads, exps=exps)
+                    K.conv_igemm_f16x3_qkv(seg, pi.f3, pi.b, qkv3, Hm=H, Wm=W, a_exp=a_exp, C=C, heads=p.heads,
+                                           exps=exps)
                 if forms.current().proj_pa and K.proj_pa_ok(Y, C) and C % 32 == 0:
                     # the attention writes O already scaled and split in the out-projection's LDS
                     # stage order (no fp32 O round trip, no split pass); the GEMM copies it by LDS-DMA
                     a3o = K.attention_presplit_a3(qkv3, B, N, C, p.heads, exps)
                     del qkv3
-                    gp = K.GnPart.of(Y)
-                    fused = K.gn_conv_ok(Y, gp, p.w_out_f3.N, H, W, 256 if p.w_out_f3.N <= 64 else 128)
+                    gp = K.gn_epilogue(Y, po.f3.N, H, W, K.igemm_bm(po.f3.N))
                     shape = View(a3o.view(torch.float32).view(B, H, W, C), 0, C)  # the operand's view shape
-                    K.proj_f16x3(shape, a3o, p.w_out_f3, p.b_out, Y, a_exp=exps[2], res=Y, absmax=absmax,
-                                 gn=gp if fused else None)
-                    self._gn_fill(Y, fused)
+                    K.proj_f16x3(shape, a3o, po.f3, po.b, Y, a_exp=exps[2], res=Y, absmax=absmax, gn=gp)
+                    self._gn_fill(Y, gp is not None)
                     return absmax is not None
                 o = self._new(B, H, W, C)
                 K.attention_presplit(qkv3, o.view(B * N, C), B, N, C, p.heads, exps)
             else:
                 o = self._new(B, H, W, C)
                 qkv = self._new(B, H, W, 3 * C)
-                K.conv_igemm_f16x3([seg], p.w_in_f3, p.b_in, View.full(qkv), Hm=H, Wm=W, a_exp=a_exp)
+                K.conv_igemm_f16x3([seg], pi.f3, pi.b, View.full(qkv), Hm=H, Wm=W, a_exp=a_exp)
                 K.attention(qkv.view(B * N, 3 * C), o.view(B * N, C), B, N, C, p.heads, 'f16x3', exps)
-            gp = K.GnPart.of(Y)
-            fused = K.gn_conv_ok(Y, gp, p.w_out_f3.N, H, W, 256 if p.w_out_f3.N <= 64 else 128)
-            K.conv_igemm_f16x3([Seg(View.full(o), TAPS1)], p.w_out_f3, p.b_out, Y, Hm=H, Wm=W, a_exp=exps[2],
-                               res=Y, absmax=absmax, gn=gp if fused else None)
-            self._gn_fill(Y, fused)
+            gp = K.gn_epilogue(Y, po.f3.N, H, W, K.igemm_bm(po.f3.N))
+            K.conv_igemm_f16x3([Seg(View.full(o), TAPS1)], po.f3, po.b, Y, Hm=H, Wm=W, a_exp=exps[2], res=Y,
+                               absmax=absmax, gn=gp)
+            self._gn_fill(Y, gp is not None)
             return absmax is not None
         qkv = self._new(B, H, W, 3 * C)
         o = self._new(B, H, W, C)
-        self.conv([Seg(Y, TAPS1, scale=sc, shift=sh, silu=False)], p.w_in, p.w_in_x6, p.b_in, View.full(qkv), H, W)
+        self.conv([Seg(Y, TAPS1, scale=sc, shift=sh, silu=False)], pi, View.full(qkv), H, W)
         K.attention(qkv.view(B * N, 3 * C), o.view(B * N, C), B, N, C, p.heads, self.precision)
-        return self.conv([Seg(View.full(o), TAPS1)], p.w_out, p.w_out_x6, p.b_out, Y, H, W, res=Y, absmax=absmax)[0]
+        return self.conv([Seg(View.full(o), TAPS1)], po, Y, H, W, res=Y, absmax=absmax)[0]
 
     # ------------------------------------------------------------------ forward
     def max_batch(self, S: int, S2: int) -> int:
@@ -575,73 +574,74 @@ class UnetEngine:
         def bound_slot(needed: bool):
             return amax[next(slots)] if (needed and amax is not None) else None
 
+        def layer(cur: View, tgt: View, stage, li: int, slot):
+            """ResBlock li of a stage into tgt, then the layer's attention in place where it has one.
+            Returns slot when the last of the two emitted tgt's per-image absmax into it, else None."""
+            res, att = stage
+            ap = att[li] if li < len(att) else None
+            emitted = self.resblock(cur, tgt, res[li], temb, temb_ld, absmax=None if ap is not None else slot)
+            if ap is not None:
+                emitted = self.attention(tgt, ap, absmax=slot)
+            return slot if emitted else None
+
         # ---------------- down path
         for i in range(L):
-            res, att = self.downs[i]
+            stage, dn = self.downs[i], self.down_convs[i]
+            n_res = len(stage[0])
             co = dc[i + 1]
             H, W = sizes[i]
             final = View(U[i + 1], dc[i + 1], dc[i + 1]) if i < L - 1 else View.full(
                 self._new(B, sizes[i + 1][0], sizes[i + 1][1], co, gn_sw=self._sw(co)))
             bnd = None
-            for li, rp in enumerate(res):
-                last = li == len(res) - 1
-                tgt = final if (last and self.down_convs[i] is None) else View.full(
-                    self._new(B, H, W, co, gn_sw=self._sw(co)))
-                slot = bound_slot(last and self.down_convs[i] is not None)
-                bnd = slot if self.resblock(cur, tgt, rp, temb, temb_ld, absmax=None if att else slot) else None
-                if att:
-                    bnd = slot if self.attention(tgt, att[li], absmax=slot) else None
+            for li in range(n_res):
+                last = li == n_res - 1
+                tgt = final if (last and dn is None) else View.full(self._new(B, H, W, co, gn_sw=self._sw(co)))
+                bnd = layer(cur, tgt, stage, li, bound_slot(last and dn is not None))
                 cur = tgt
-            if self.down_convs[i] is not None:
-                w, b, w6, w3, w3s = self.down_convs[i]
+            if dn is not None:
                 seg = Seg(cur, TAPS4S2, stride=2)
                 Hm, Wm = sizes[i + 1]
-                if w3s is not None and bnd is not None and K.conv4x4s2_f16x3_ok(seg, w3s.N, Hm, Wm):
-                    gp = K.GnPart.of(final)
-                    fused = K.gn_conv_ok(final, gp, w3s.N, Hm, Wm)
-                    K.conv4x4s2_f16x3(seg, w3s, b, final, Hm=Hm, Wm=Wm, a_bound=bnd, gn=gp if fused else None)
-                    self._gn_fill(final, fused)
+                if dn.f3s is not None and bnd is not None and K.conv4x4s2_f16x3_ok(seg, dn.f3s.N, Hm, Wm):
+                    gp = K.gn_epilogue(final, dn.f3s.N, Hm, Wm)
+                    K.conv4x4s2_f16x3(seg, dn.f3s, dn.b, final, Hm=Hm, Wm=Wm, a_bound=bnd, gn=gp)
+                    self._gn_fill(final, gp is not None)
                 else:
-                    self.resample([seg], (w, w6, w3), b, final, Hm, Wm, bnd)
+                    self.resample([seg], dn, final, Hm, Wm, bnd)
                 cur = final
 
         # ---------------- mid path
         bnd = None
-        for j, (res, att) in enumerate(self.mids):
-            last_mid = j == len(self.mids) - 1
+        for j, stage in enumerate(self.mids):
+            res = stage[0]
             H, W = cur.H, cur.W
             for li, rp in enumerate(res):
-                if last_mid and li == len(res) - 1 and self.up_convs[0] is None:
+                last = j == len(self.mids) - 1 and li == len(res) - 1
+                if last and self.up_convs[0] is None:
                     tgt = View(U[L - 1], 0, dc[L - 1])
                 else:
                     tgt = View.full(self._new(B, H, W, rp.co, gn_sw=self._sw(rp.co)))
-                has_att = li < len(att)
-                slot = bound_slot(last_mid and li == len(res) - 1 and self.up_convs[0] is not None)
-                bnd = slot if self.resblock(cur, tgt, rp, temb, temb_ld, absmax=None if has_att else slot) else None
+                bnd = layer(cur, tgt, stage, li, bound_slot(last and self.up_convs[0] is not None))
                 cur = tgt
-                if has_att:
-                    bnd = slot if self.attention(cur, att[li], absmax=slot) else None
 
         # ---------------- up path
-        for k, (res, att) in enumerate(self.ups):
+        for k, stage in enumerate(self.ups):
+            res, up = stage[0], self.up_convs[k]
             i = L - 1 - k
             H, W = sizes[i]
-            if self.up_convs[k] is not None:
-                parts, b, w3t = self.up_convs[k]
+            if up is not None:
                 dst = View(U[i], 0, dc[i])
                 seg = Seg(cur, [(0, 0)])
-                if w3t is not None and bnd is not None and K.convT4x4s2_f16x3_ok(seg, w3t.N):
-                    gp = K.GnPart.of(dst)
-                    fused = K.gn_conv_ok(dst, gp, w3t.N, dst.H, dst.W)
-                    K.convT4x4s2_f16x3(seg, w3t, b, dst, a_bound=bnd, gn=gp if fused else None)
-                    self._gn_fill(dst, fused)
+                if up.f3t is not None and bnd is not None and K.convT4x4s2_f16x3_ok(seg, up.f3t.N):
+                    gp = K.gn_epilogue(dst, up.f3t.N, dst.H, dst.W)
+                    K.convT4x4s2_f16x3(seg, up.f3t, up.b, dst, a_bound=bnd, gn=gp)
+                    self._gn_fill(dst, gp is not None)
                 else:
                     np_in = cur.H * cur.W // 64 if (cur.H * cur.W) % 64 == 0 else 0
                     fused = []
-                    for par, ((py, px), (taps, w, w6, w3)) in enumerate(zip(((0, 0), (0, 1), (1, 0), (1, 1)), parts)):
+                    for par, ((py, px), (taps, p)) in enumerate(zip(((0, 0), (0, 1), (1, 0), (1, 1)), up.parts)):
                         # each parity covers a quarter of the output pixels: its own range of pixel blocks
-                        fused.append(self.resample([Seg(cur, taps)], (w, w6, w3), b, dst, cur.H, cur.W, bnd,
-                                                   gn_p64=par * np_in, gn_defer=True, out_map=(2, 2, py, px)))
+                        fused.append(self.resample([Seg(cur, taps)], p, dst, cur.H, cur.W, bnd, gn_p64=par * np_in,
+                                                   gn_defer=True, out_map=(2, 2, py, px)))
                     self._gn_fill(dst, all(fused) and np_in > 0)
             else:
                 assert cur.t is U[i] and cur.c0 == 0, 'non-upsampling level must have been written in place'
@@ -653,10 +653,7 @@ class UnetEngine:
                 last = li == len(res) - 1
                 tgt = View(U[i - 1], 0, dc[i - 1]) if (last and next_in_place) else View.full(
                     self._new(B, H, W, rp.co, gn_sw=self._sw(rp.co)))
-                slot = bound_slot(last and next_up)
-                bnd = slot if self.resblock(cur, tgt, rp, temb, temb_ld, absmax=None if att else slot) else None
-                if att:
-                    bnd = slot if self.attention(tgt, att[li], absmax=slot) else None
+                bnd = layer(cur, tgt, stage, li, bound_slot(last and next_up))
                 cur = tgt
 
         # ---------------- head: GN -> SiLU -> conv_out, NCHW output
@@ -664,10 +661,10 @@ class UnetEngine:
         out = torch.empty((B, m.model_config.im_channels, S, S2), dtype=torch.float32, device=self.device)
         head = [Seg(cur, TAPS3, scale=sc, shift=sh, silu=True)]
         if self.conv_out_head is not None:
-            K.head_conv(cur, sc, sh, self.conv_out_head, self.conv_out_b, out)
-        elif self.conv_out_f3 is not None:
-            K.conv_igemm_f16x3(head, self.conv_out_f3, self.conv_out_b, None, Hm=S, Wm=S2, out_nchw=out,
-                               a_exp=K.f16x3_a_exp(*self.norm_out_gb, S * S2 * cur.C // 8))
+            K.head_conv(cur, sc, sh, self.conv_out_head, self.conv_out.b, out)
+        elif self.conv_out.f3 is not None:
+            K.conv_igemm_f16x3(head, self.conv_out.f3, self.conv_out.b, None, Hm=S, Wm=S2, out_nchw=out,
+                               a_exp=K.f16x3_a_exp(*self.conv_out.gb, S * S2 * cur.C // 8))
         else:
-            self.conv(head, self.conv_out_w, self.conv_out_x6, self.conv_out_b, None, S, S2, out_nchw=out)
+            self.conv(head, self.conv_out, None, S, S2, out_nchw=out)
         return out

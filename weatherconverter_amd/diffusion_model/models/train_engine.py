@@ -337,13 +337,6 @@ class TrainEngine:
             K.GnPart.attach(t, sw)
         return t
 
-    @staticmethod
-    def _gn_out(out: View, N: int, H: int, W: int, bm: Optional[int] = None) -> Optional['K.GnPart']:
-        """out's tile partials when the conv writing it can emit them from its epilogue, else None
-        (bm: the implicit GEMM's M tile)."""
-        gp = K.GnPart.of(out)
-        return gp if K.gn_conv_ok(out, gp, N, H, W, bm) else None
-
     def _zrow(self, B: int) -> torch.Tensor:
         """A zeroed float32[B] on the device (a per-image bound that writers raise): rows of one pooled
         zero fill instead of a fill launch each.  A row is never handed out twice."""
@@ -573,11 +566,11 @@ class TrainEngine:
         b1 = rp['conv1'].bias.detach().float().contiguous()
         gp1 = None  # h's GroupNorm partials, when conv1's epilogue wrote them
         if rp.has('wn_1') and K.wino_eligible(seg1, co, H, W):
-            gp1 = self._gn_out(h, co, H, W)
+            gp1 = K.gn_epilogue(h, co, H, W)
             K.conv3x3_wino(seg1, rp['wn_1'], b1, h, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*rp['gb1'], H * W * X.C // 8),
                            temb=temb[:, rp['off']:], temb_ld=temb.shape[1], gn=gp1)
         elif rp.has('f3_1') and K.x6_eligible(seg1, co, H, W):
-            gp1 = self._gn_out(h, co, H, W)
+            gp1 = K.gn_epilogue(h, co, H, W)
             K.conv3x3_f16x3(seg1, rp['f3_1'], b1, h, Hm=H, Wm=W,
                             a_exp=K.f16x3_a_exp(*rp['gb1'], H * W * X.C // 8), temb=temb[:, rp['off']:],
                             temb_ld=temb.shape[1], gn=gp1)
@@ -587,14 +580,14 @@ class TrainEngine:
         seg2 = [Seg(h, TAPS3, scale=st2[0], shift=st2[1], silu=True), Seg(X, TAPS1, kbase=9 * co)]
         gp2 = None  # Y's partials (an attention block's input): the next GroupNorm's statistics
         if rp.has('wn_2') and K.wino_eligible(seg2, co, H, W):
-            gp2 = self._gn_out(Y, co, H, W)
+            gp2 = K.gn_epilogue(Y, co, H, W)
             K.conv3x3_wino(seg2, rp['wn_2'], rp['b2'], Y, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*rp['gb2'], H * W * co // 8),
                            a_bound=st1[4], absmax=amx, gn=gp2)
             if amx is not None:
                 self._raised[id(amx)] = True
         elif rp.has('f3_2') and K.x6_eligible(seg2, co, H, W):
             # the residual segment (raw X) in fp16 under GN1's per-image bound of |X|
-            gp2 = self._gn_out(Y, co, H, W)
+            gp2 = K.gn_epilogue(Y, co, H, W)
             K.conv3x3_f16x3(seg2, rp['f3_2'], rp['b2'], Y, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*rp['gb2'], H * W * co // 8),
                             a_bound=st1[4], absmax=amx, gn=gp2)
             if amx is not None:
@@ -625,7 +618,7 @@ class TrainEngine:
             exps = K.attention_exps_from_norms(ap['qkv_l1'], ap['qkv_babs'], ap['gb'][0], ap['gb'][1], ng)
             K.attention_fwd_lse(qkv.view(B * N, 3 * C), o.view(B * N, C), lse, B, N, C, ap['heads'],
                                 precision='f16x3', exps=exps)
-            gpo = self._gn_out(Yout, C, H, W, 256 if C <= 64 else 128)
+            gpo = K.gn_epilogue(Yout, C, H, W, K.igemm_bm(C))
             K.conv_igemm_f16x3([Seg(View.full(o), TAPS1)], ap['f3_out'], b_out, Yout, Hm=H, Wm=W, a_exp=exps[2],
                                res=Ypre, absmax=amx, gn=gpo)
             if amx is not None:

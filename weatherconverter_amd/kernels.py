@@ -322,6 +322,12 @@ def _abytes(segs: Sequence[Seg], N: int, out_pixels: int, res: Optional[View] = 
     return b
 
 
+def igemm_bm(N: int) -> int:
+    """M tile (output pixels) of the implicit-GEMM convs for N output channels, over an N tile of 64 or
+    128 (mirrors dispatch() in csrc/wc_conv.hip)."""
+    return 256 if N <= 64 else 128
+
+
 def conv_igemm(segs: Sequence[Seg], w: torch.Tensor, bias: Optional[torch.Tensor], out: View, *, Hm: int, Wm: int,
                temb: Optional[torch.Tensor] = None, temb_ld: int = 0, res: Optional[View] = None,
                out_map=(1, 1, 0, 0), out_nchw: Optional[torch.Tensor] = None, act: int = 0,
@@ -333,7 +339,8 @@ def conv_igemm(segs: Sequence[Seg], w: torch.Tensor, bias: Optional[torch.Tensor
     a = _conv_args(segs, N, bias, out, Hm, Wm, temb, temb_ld, res, out_map, out_nchw, act, act_param=act_param)
     a.w, a.ldw = w.data_ptr(), ldw
     # the kernel symbol wc_conv_igemm dispatches to (mirrors dispatch() in csrc/wc_conv.hip)
-    bm, bn = (256, 64) if N <= 64 else (128, 128)
+    bm = igemm_bm(N)
+    bn = 64 if bm == 256 else 128
     s0 = segs[0]
     pro = 0 if s0.scale is None else (2 if s0.silu else 1)
     unib = 'true' if (Hm * Wm) % bm == 0 else 'false'
@@ -852,7 +859,8 @@ def conv_igemm_f16x3(segs: Sequence[Seg], w3: X6Weight, bias: Optional[torch.Ten
     _req(w3.C0 == segs[0].view.C and w3.C1 == (segs[1].view.C if len(segs) == 2 else 0), 'f16x3 weight segments')
     a = _conv_args(segs, w3.N, bias, out, Hm, Wm, temb, temb_ld, res, out_map, out_nchw, 0, absmax, gn=gn,
                    gn_p64=gn_p64)
-    bm, bn = (256, 64) if w3.N <= 64 else (128, 128)
+    bm = igemm_bm(w3.N)
+    bn = 64 if bm == 256 else 128
     s0 = segs[0]
     pro = 0 if s0.scale is None else (2 if s0.silu else 1)
     unib = 'true' if (Hm * Wm) % bm == 0 else 'false'
@@ -1086,7 +1094,8 @@ def conv_igemm_x6(segs: Sequence[Seg], w6: X6Weight, bias: Optional[torch.Tensor
     _req(w6.C0 == segs[0].view.C and w6.C1 == (segs[1].view.C if len(segs) == 2 else 0), 'x6 weight segments')
     a = _conv_args(segs, w6.N, bias, out, Hm, Wm, temb, temb_ld, res, out_map, out_nchw, act, absmax, gn=gn,
                    gn_p64=gn_p64)
-    bm, bn = (256, 64) if w6.N <= 64 else (128, 128)
+    bm = igemm_bm(w6.N)
+    bn = 64 if bm == 256 else 128
     s0 = segs[0]
     pro = 0 if s0.scale is None else (2 if s0.silu else 1)
     unib = 'true' if (Hm * Wm) % bm == 0 else 'false'
@@ -1108,6 +1117,13 @@ def gn_conv_ok(out: Optional[View], gn: Optional[GnPart], N: int, Hm: int, Wm: i
     (mirrors the host checks of wc_conv3x3_x6 / wc_conv_igemm_x6; bm = the implicit GEMM's M tile)."""
     return (gn is not None and out is not None and gn.covers(out) and N == out.C and N % 32 == 0
             and (Hm * Wm) % 64 == 0 and (bm is None or (Hm * Wm) % bm == 0))
+
+
+def gn_epilogue(out: Optional[View], N: int, Hm: int, Wm: int, bm: Optional[int] = None) -> Optional[GnPart]:
+    """out's tile partials when the split-precision conv writing it can emit them from its epilogue
+    (gn_conv_ok; bm: the implicit GEMM's M tile, igemm_bm), else None: the conv's `gn` argument."""
+    gp = GnPart.of(out)
+    return gp if gn_conv_ok(out, gp, N, Hm, Wm, bm) else None
 
 
 def gn_affine(v: View, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float = 1e-5,
