@@ -540,10 +540,16 @@ class UnetEngine:
             outs.append(self._forward(x[b0:b0 + cap], tc))
         return torch.cat(outs)
 
-    def _forward(self, x: torch.Tensor, tt: torch.Tensor) -> torch.Tensor:
+    def refresh(self) -> None:
+        """Repack, on the current stream, if a parameter changed since the last pack (every forward starts
+        with this; a caller that forks streams calls it before the fork, so that no stream reads packs
+        another one is still writing)."""
         if self._signature() != self._sig:  # parameters changed in place: repack
             self._sig = self._signature()
             self._pack()
+
+    def _forward(self, x: torch.Tensor, tt: torch.Tensor) -> torch.Tensor:
+        self.refresh()
         m = self.model
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         B, _, S, S2 = x.shape

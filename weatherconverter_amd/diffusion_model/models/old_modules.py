@@ -119,6 +119,13 @@ class UNet(DiffusionUNet):
         self._engine = None
         return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
+    def invalidate_packs(self) -> 'UNet':
+        """Drop the engine and its packed weights (folded BatchNorm included); the next forward packs from
+        the live parameters and buffers.  Needed only after an in-place write through ``.data`` or a raw
+        pointer, which the engine's signature cannot see ("When weights change")."""
+        self._engine = None
+        return self
+
 
 TAPS3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
 
@@ -141,7 +148,9 @@ class OldUnetEngine:
         self._pack()
 
     def _signature(self):
-        return tuple((q.data_ptr(), q._version) for q in self.m.parameters())
+        # the buffers too: the BatchNorm running statistics are folded into the packs
+        return tuple((q.data_ptr(), q._version) for q in self.m.parameters()) + tuple(
+            (b.data_ptr(), b._version) for b in self.m.buffers())
 
     def _pack(self):
         m, dev = self.m, self.dev

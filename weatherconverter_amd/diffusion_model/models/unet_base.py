@@ -204,10 +204,19 @@ class Unet(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):
         # device / dtype moves invalidate the packed GPU weights
-        self._engine = None
-        self._train_engine = None
+        self.invalidate_packs()
         return super()._apply(fn, *args, **kwargs)
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        self._engine = None
+        self.invalidate_packs()
         return super().load_state_dict(state_dict, strict=strict, assign=assign)
+
+    def invalidate_packs(self) -> 'Unet':
+        """Drop the engines and with them every packed weight and weight-derived range exponent; the next
+        forward packs from the live parameters.  Needed only after a write the engines cannot see: an
+        in-place write through ``p.data`` or a raw pointer, which moves neither the parameter's version
+        counter nor its address ("When weights change").  A ``_GraphStep`` captured
+        before the call still belongs to the old weights."""
+        self._engine = None
+        self._train_engine = None
+        return self

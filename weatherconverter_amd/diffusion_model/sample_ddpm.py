@@ -99,6 +99,10 @@ class _GraphStep:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
+                if self.split > 1 and not (model.training and torch.is_grad_enabled()):
+                    # build or refresh the engine's packs here, before _forward forks the group streams:
+                    # otherwise the first group's stream would pack while the others already read
+                    model.engine().refresh()
                 for _ in range(2):  # warm the allocator / engine pack outside capture
                     self.eps = self._forward()
             torch.cuda.current_stream().wait_stream(s)

@@ -87,6 +87,13 @@ class Generator(nn.Module):
         self._engine = None  # device moves invalidate the packed weights
         return super()._apply(fn, *args, **kwargs)
 
+    def invalidate_packs(self) -> 'Generator':
+        """Drop the engine and its packed weights (folded BatchNorm, PReLU slopes); the next forward packs
+        from the live parameters and buffers.  Needed only after an in-place write through ``.data`` or a
+        raw pointer, which SrganEngine.stale() cannot see ("When weights change")."""
+        self._engine = None
+        return self
+
 
 class SrganEngine:
     """Packed HIP execution of an eval-mode ``Generator`` (NHWC fp32 activations)."""
