@@ -28,7 +28,8 @@ Precision bf16x6 / fp32: bf16x6 / fp32 MFMA throughout.  fp32-class gradients, c
 PyTorch autograd of the reference restatement in float64.  Every gradient buffer is written in a
 fixed order: results are deterministic run to run.
 """
-from typing import Dict, List, Optional, Tuple
+from dataclasses import dataclass, field
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -40,47 +41,159 @@ from .engine import TAPS1, TAPS3, TAPS4S2, UnetEngine, check_supported, pack_con
 _PARITIES = ((0, 0), (0, 1), (1, 0), (1, 1))
 
 
-class _Pack(dict):
-    """A layer's packing record whose weight packs are built on first use: a value wrapped in
-    _Pack.lazy(fn) is computed by fn() when read, then cached.  Each training step packs only the
-    forms its arithmetic actually launches (e.g. the f16x3 data-gradient packs, not also the bf16x6
-    ones) — the packing is host-launched torch work on every step."""
+def _f32(p: torch.Tensor) -> torch.Tensor:
+    """A parameter as the fp32 tensor the kernels read (no copy when it already is one)."""
+    return p.detach().float()
 
-    class lazy:
-        __slots__ = ('fn', )
 
-        def __init__(self, fn):
-            self.fn = fn
+def _one_image_tiles(H: int, W: int, C: int) -> bool:
+    """The implicit GEMM's M tiles (kernels.igemm_bm of C) lie inside one image each: a per-image A bound holds."""
+    return (H * W) % (256 if C <= 64 else 128) == 0
 
-    def __getitem__(self, k):
-        v = dict.__getitem__(self, k)
-        if isinstance(v, _Pack.lazy):
-            with torch.no_grad():
-                v = v.fn()
-            dict.__setitem__(self, k, v)
+
+class ConvForms:
+    """One conv's weight in every form the training step can launch, named as engine.ConvPack / UpPack name
+    them.  A form is given as a builder fn(this record), run (under no_grad) on first read and cached: a
+    training step packs only the forms it launches (the f16x3 data-gradient packs, not also the bf16x6 ones;
+    packing is host-launched work on every step).  A builder may read another form (a ResBlock conv's packs
+    all read its re-layout w), which is then built once.  A form assigned ahead of time (c.wn = pack) is kept."""
+    # w [N][K] fp32 (wc_conv_igemm), x6 (wc_conv_igemm_x6), f3 / f3h f16x3 in natural / halo order, wn Winograd,
+    # f3s space-to-depth 4x4/s2, f3t one-launch ConvT, parts its four parities as (taps, ConvForms).  A builder
+    # gets the record as its argument instead of closing over it, so a record is no reference cycle and a
+    # step's packs are freed as soon as the next step's replace them.
+    FORMS = ('w', 'x6', 'f3', 'f3h', 'wn', 'f3s', 'f3t', 'parts')
+
+    def __init__(self, **builders: Optional[Callable]):  # None: the conv does not have that form
+        assert set(builders) <= set(self.FORMS), sorted(builders)
+        self._builders = {k: fn for k, fn in builders.items() if fn is not None}
+
+    def has(self, form: str) -> bool:
+        """Whether the conv was given this form, without building it."""
+        assert form in self.FORMS, form
+        return form in self.__dict__ or form in self._builders
+
+    def __getattr__(self, form: str):  # reached only while `form` is not built (not in __dict__)
+        fn = self.__dict__.get('_builders', {}).get(form)
+        if fn is None:
+            raise AttributeError(f'ConvForms: this conv was not given form {form!r}')
+        with torch.no_grad():
+            v = fn(self)
+        setattr(self, form, v)
         return v
 
-    def has(self, k) -> bool:
-        """Whether form k exists for this layer, without building it (a lazy form is never None)."""
-        return dict.get(self, k) is not None
+
+@dataclass
+class ResTrain:
+    """A ResBlock: conv1, conv2 (+ the 1x1 residual as in engine.ResPack) and their data gradients d1, d2
+    (the 3x3 conv with W flipped and transposed) and dr (the residual's: dY W)."""
+    ci: int
+    co: int
+    off: int  # first column of this block's time-embedding projection in temb / dproj
+    gn1: torch.nn.Module
+    gn2: torch.nn.Module
+    mod1: torch.nn.Module
+    mod2: torch.nn.Module
+    modr: torch.nn.Module
+    temb: torch.nn.Module
+    b2: torch.Tensor  # conv2's bias + the residual conv's
+    conv1: ConvForms
+    conv2: ConvForms
+    d1: ConvForms
+    d2: ConvForms
+    dr: ConvForms
+    wino_raw: List[Tuple[ConvForms, tuple]]  # the kernels.pack_wino_raw request of every wn form (forms.pack_raw)
+    gb1: Tuple[float, float] = (0.0, 0.0)  # (max|gamma|, max|beta|) of gn1 / gn2, on the host (_pack)
+    gb2: Tuple[float, float] = (0.0, 0.0)
 
 
-class _Slot:
-    """A host value of the packing pass, filled by TrainEngine._resolve."""
-    __slots__ = ('value', )
+@dataclass
+class AttnTrain:
+    C: int
+    heads: int
+    gn: torch.nn.Module
+    mha: torch.nn.Module
+    proj_in: ConvForms  # f3: under the GN bound
+    proj_out: ConvForms  # f3: under the V bound
+    d_in: ConvForms  # the projections' data gradients (dY W); f3: under per-image absmax bounds
+    d_out: ConvForms
+    qkv_l1: Optional[torch.Tensor] = None  # f16x3: host row-L1 norms of W_in and |b_in| (bounds)
+    qkv_babs: Optional[torch.Tensor] = None
+    gb: Tuple[float, float] = (0.0, 0.0)
 
 
+@dataclass
+class ScaleTrain:
+    """A 4x4 / stride-2 Conv2d (down) or ConvTranspose2d (up) and its data gradient, the other of the two on the
+    same weight.  The conv: w / x6 / f3s; the transposed conv: f3t / parts ((taps, ConvForms) per output parity)."""
+    mod: torch.nn.Module
+    fwd: ConvForms
+    dgrad: ConvForms
+
+
+@dataclass
+class HeadTrain:
+    small: bool  # the fp32 VALU head kernels (forms.train_smallconv) instead of the implicit GEMMs
+    w: torch.Tensor  # conv_out's weight as the forward read it (wc_head_dgrad)
+    wp: Optional[torch.Tensor] = None  # small: kernels.pack_head
+    fwd: Optional[ConvForms] = None  # not small: the conv, and its data gradient over the 32-channel
+    dgrad: Optional[ConvForms] = None  # padded loss gradient
+
+
+class ConvInRec(NamedTuple):
+    x: torch.Tensor
+    out: View
+
+
+class ResRec(NamedTuple):
+    X: View
+    h: View
+    Y: View
+    rp: ResTrain
+    st1: tuple  # gn1's (scale, shift, rstd, -mean*rstd, per-image bound of |X|)
+    st2: tuple
+
+
+class AttnRec(NamedTuple):
+    Ypre: View
+    Yout: View
+    qkv: torch.Tensor
+    o: torch.Tensor
+    lse: torch.Tensor
+    st: tuple
+    ap: AttnTrain
+
+
+class DownRec(NamedTuple):
+    cur: View
+    out: View
+    sp: ScaleTrain
+    bcur: Optional[torch.Tensor]  # the forward's per-image max |cur|
+
+
+class UpRec(DownRec):
+    """The same fields for a ConvTranspose."""
+
+
+class HeadRec(NamedTuple):
+    cur: View
+    st: tuple
+    hp: HeadTrain
+
+
+@dataclass
 class Tape:
-    """Everything one training forward saved for its backward: the layer records (activations, GN
-    statistics, packed weights) plus the inputs and the per-step weight packs the backward reads.  One
-    per forward, owned by that forward's autograd node, consumed by exactly one backward."""
-    _FIELDS = ('records', 'x', 'tt', 'U', 'P', 'head_T', 'tproj', 'temb_w', 'res_rows')
-
-    def __init__(self, engine: 'TrainEngine'):
-        self.records = engine.tape
-        for f in self._FIELDS[1:]:
-            setattr(self, f, getattr(engine, f))
-        self.consumed = False
+    """Everything one training forward saved for its backward: the layer records in forward order
+    (activations, GN statistics, that forward's packed weights; ConvInRec first, HeadRec last) plus the
+    timesteps and the time-embedding packs.  One per forward, owned by that forward's autograd node,
+    consumed by exactly one backward; the engine keeps nothing of a forward but last_tape."""
+    tt: torch.Tensor
+    P: int
+    tproj: List[torch.Tensor]
+    temb_w: torch.Tensor
+    res_rows: List[ResTrain]
+    records: list = field(default_factory=list)
+    raised: Dict[int, bool] = field(default_factory=dict)  # forward only: the bounds (_zrow) a kernel raised
+    consumed: bool = False
 
 
 class TrainEngine:
@@ -108,150 +221,126 @@ class TrainEngine:
         self.f3 = p == 'f16x3'
         # data gradients on f16x3 under per-image absmax bounds of the incoming gradient (mode f16x3)
         self.f3d = self.f3 and forms.current().dgrad_f16x3
-        self.tape: List[tuple] = []
         self.last_tape: Optional[Tape] = None
 
     # ------------------------------------------------------------------ packing (per step)
-    def _pk(self, w2d: torch.Tensor, C0: int, ntaps: int, C1: int = 0):
-        w2d = w2d.contiguous().float()
-        x6 = None
-        if self.precision == 'bf16x6' and C0 % 16 == 0 and C1 % 16 == 0:
-            x6 = K.pack_x6(w2d, C0, C1, ntaps=ntaps, order='natural')
-        elif C0 % 32 or C1 % 32:
-            raise RuntimeError(f'fp32 implicit GEMM needs channel counts % 32 (got {C0}, {C1})')
-        return (w2d, x6)
+    def _igemm(self, w2d: Callable, C0: int, ntaps: int, C1: int = 0, **more) -> ConvForms:
+        """An implicit-GEMM conv: w = w2d(), the [N][ntaps*C0 + C1] weight (pack_conv), and on bf16x6 its x6
+        pack; more: the builders of its other forms."""
+        x6 = self.precision == 'bf16x6' and C0 % 16 == 0 and C1 % 16 == 0
 
-    def _conv(self, segs, pk, bias, out: Optional[View], H: int, W: int, **kw):
-        w, x6 = pk
+        def w(c):
+            if not x6 and (C0 % 32 or C1 % 32):
+                raise RuntimeError(f'fp32 implicit GEMM needs channel counts % 32 (got {C0}, {C1})')
+            return w2d().contiguous().float()
+
+        return ConvForms(w=w, x6=(lambda c: K.pack_x6(c.w, C0, C1, ntaps=ntaps, order='natural')) if x6 else None,
+                         **more)
+
+    def _igemm_now(self, w2d: torch.Tensor, C0: int, ntaps: int) -> ConvForms:
+        """_igemm of a weight at hand, packed now and not at its first launch."""
+        c = self._igemm(lambda: w2d, C0, ntaps)
+        _ = c.x6 if c.has('x6') else c.w
+        return c
+
+    def _parts(self, wt: torch.Tensor, C0: int):
+        """The four output parities of the ConvTranspose with weight wt as implicit-GEMM convs: the
+        `parts` form, all four packed before the first is launched."""
+        return [(taps, self._igemm_now(wp, C0, len(taps)))
+                for taps, wp in (pack_convT(wt, py, px) for py, px in _PARITIES)]
+
+    def _conv(self, segs, c: ConvForms, bias, out: Optional[View], H: int, W: int, **kw):
         if kw.get('absmax', 0) is None:  # no bound tracked (outside the f16x3 backward)
-            del kw['absmax']
-        if x6 is not None:
-            K.conv_igemm_x6(segs, x6, bias, out, Hm=H, Wm=W, **kw)
+            kw.pop('absmax')
+        if c.has('x6'):
+            K.conv_igemm_x6(segs, c.x6, bias, out, Hm=H, Wm=W, **kw)
         else:
-            K.conv_igemm(segs, w, bias, out, Hm=H, Wm=W, **kw)
+            K.conv_igemm(segs, c.w, bias, out, Hm=H, Wm=W, **kw)
 
-    def _pack_res(self, blk, i: int):
+    def _pack_res(self, blk, i: int, off: int) -> ResTrain:
         f, s, r = blk.resnet_conv_first[i], blk.resnet_conv_second[i], blk.residual_input_conv[i]
         w1, w2, wr = f[2].weight.detach(), s[2].weight.detach(), r.weight.detach()
         ci, co = w1.shape[1], w1.shape[0]
         wr2 = wr.reshape(co, ci)
-        f3 = self.f3 and ci % 16 == 0 and co % 16 == 0
+        f3, f3d = self.f3 and ci % 16 == 0 and co % 16 == 0, self.f3d
         wino = forms.current().wino
         raw = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (w1, w2)) \
             and 9 * (max(ci, co) + 4) * 4 <= 64 * 1024 and forms.current().pack_raw
-        L = _Pack.lazy
-        # shared re-layouts, each built once and only if a pack that needs it is (the Winograd forms
-        # usually replace the direct f16x3 ones, so those are lazy too)
-        rp = _Pack(w1c=L(lambda: pack_conv(w1).float().contiguous()),
-                   w2cat=L(lambda: torch.cat([pack_conv(w2), wr2], 1).float().contiguous()),
-                   w1T=L(lambda: pack_conv(w1.flip([2, 3]).transpose(0, 1)).float().contiguous()),
-                   w2T=L(lambda: pack_conv(w2.flip([2, 3]).transpose(0, 1)).float().contiguous()))
-        rp.update(
-            ci=ci, co=co, gn1=f[0], conv1=f[2], gn2=s[0], conv2=s[2], resc=r, temb=blk.t_emb_layers[i][1],
-            pk1=L(lambda: self._pk(rp['w1c'], ci, 9)),
-            pk2=L(lambda: self._pk(rp['w2cat'], co, 9, ci)),
-            f3_1=L(lambda: K.pack_f16x3(rp['w1c'], ci)) if f3 else None,
-            f3_2=L(lambda: K.pack_f16x3(rp['w2cat'], co, ci, res_f16=True)) if f3 else None,
-            gb1=self._later_absmax(f[0].weight, f[0].bias),
-            gb2=self._later_absmax(s[0].weight, s[0].bias),
-            b2=(s[2].bias.detach() + r.bias.detach()).float().contiguous(),
-            pk1T=L(lambda: self._pk(rp['w1T'], co, 9)),
-            pk2T=L(lambda: self._pk(rp['w2T'], co, 9)),
-            pkrT=L(lambda: self._pk(wr2.t(), co, 1)),
-            # f16x3 data gradients (raw gradient operand under its per-image absmax bound)
-            f3_1T=L(lambda: K.pack_f16x3(rp['w1T'], co)) if self.f3d else None,
-            f3_2T=L(lambda: K.pack_f16x3(rp['w2T'], co)) if self.f3d else None,
-            f3_rT=L(lambda: K.pack_f16x3(wr2.t().contiguous().float(), co, ntaps=1, order='natural'))
-            if self.f3d else None,
-            # the Winograd F(2,3)-along-x forms of the same f16x3 convs (forward and data gradients)
-            # (from the module weights directly when they are fp32 on the device: no host re-layouts)
-            wn_1=L(lambda: K.pack_wino_raw(w1) if raw else K.pack_wino(rp['w1c'], ci)) if f3 and wino else None,
-            wn_2=L(lambda: K.pack_wino_raw(w2, wr2.float().contiguous()) if raw else K.pack_wino(rp['w2cat'], co, ci))
-            if f3 and wino else None,
-            wn_1T=L(lambda: K.pack_wino_raw(w1, transposed=True) if raw else K.pack_wino(rp['w1T'], co))
-            if self.f3d and wino and ci % 16 == 0 and co % 16 == 0 else None,
-            wn_2T=L(lambda: K.pack_wino_raw(w2, transposed=True) if raw else K.pack_wino(rp['w2T'], co))
-            if self.f3d and wino and co % 16 == 0 else None)
-        if raw:  # the raw-weight requests of the forms that exist, for _pack's one batched launch
-            want = {'wn_1': (w1, None, False), 'wn_2': (w2, wr2.float().contiguous(), False),
-                    'wn_1T': (w1, None, True), 'wn_2T': (w2, None, True)}
-            rp['_wino_raw'] = {k: v for k, v in want.items() if rp.has(k)}
-        return rp
+        # w: the re-layout every other form of the conv is packed from, built once and only if one of them
+        # is (the Winograd forms usually replace the direct f16x3 ones, and pack from the module weights
+        # directly when those are fp32 on the device: no host re-layout)
+        conv1 = self._igemm(
+            lambda: pack_conv(w1), ci, 9, f3h=(lambda c: K.pack_f16x3(c.w, ci)) if f3 else None,
+            wn=(lambda c: K.pack_wino_raw(w1) if raw else K.pack_wino(c.w, ci)) if f3 and wino else None)
+        conv2 = self._igemm(
+            lambda: torch.cat([pack_conv(w2), wr2], 1), co, 9, ci,
+            f3h=(lambda c: K.pack_f16x3(c.w, co, ci, res_f16=True)) if f3 else None,
+            wn=(lambda c: K.pack_wino_raw(w2, wr2.float().contiguous()) if raw else K.pack_wino(c.w, co, ci))
+            if f3 and wino else None)
 
-    def _pack_attn(self, blk, i: int):
+        def dgrad(w, wn: bool):  # f16x3 forms: the raw gradient operand under its per-image absmax bound
+            return self._igemm(
+                lambda: pack_conv(w.flip([2, 3]).transpose(0, 1)), co, 9,
+                f3h=(lambda c: K.pack_f16x3(c.w, co)) if f3d else None,
+                wn=(lambda c: K.pack_wino_raw(w, transposed=True) if raw else K.pack_wino(c.w, co)) if wn else None)
+
+        d1 = dgrad(w1, f3d and wino and ci % 16 == 0 and co % 16 == 0)
+        d2 = dgrad(w2, f3d and wino and co % 16 == 0)
+        dr = self._igemm(lambda: wr2.t(), co, 1,
+                         f3=(lambda c: K.pack_f16x3(c.w, co, ntaps=1, order='natural')) if f3d else None)
+        want = ((conv1, (w1, None, False)), (conv2, (w2, wr2.float().contiguous(), False)),
+                (d1, (w1, None, True)), (d2, (w2, None, True))) if raw else ()
+        return ResTrain(ci, co, off, f[0], s[0], f[2], s[2], r, blk.t_emb_layers[i][1],
+                        _f32(s[2].bias + r.bias).contiguous(), conv1, conv2, d1, d2, dr,
+                        [(c, req) for c, req in want if c.has('wn')])
+
+    def _pack_attn(self, blk, i: int) -> AttnTrain:
         mha, gn = blk.attentions[i], blk.attention_norms[i]
         C = mha.embed_dim
         w_in, w_out = mha.in_proj_weight.detach(), mha.out_proj.weight.detach()
-        L = _Pack.lazy
-        d = _Pack(C=C, heads=mha.num_heads, gn=gn, mha=mha, pk_in=L(lambda: self._pk(w_in, C, 1)),
-                  pk_out=L(lambda: self._pk(w_out, C, 1)), pk_inT=L(lambda: self._pk(w_in.t(), 3 * C, 1)),
-                  pk_outT=L(lambda: self._pk(w_out.t(), C, 1)), f3_in=None, f3_out=None)
-        if self.f3d and C % 16 == 0:  # projection data gradients on f16x3 (per-image absmax bounds)
-            d['f3_inT'] = L(lambda: K.pack_f16x3(w_in.t().contiguous().float(), 3 * C, ntaps=1, order='natural'))
-            d['f3_outT'] = L(lambda: K.pack_f16x3(w_out.t().contiguous().float(), C, ntaps=1, order='natural'))
-        if self.f3 and C % 16 == 0:
-            d['f3_in'] = K.pack_f16x3(w_in.float(), C, ntaps=1, order='natural')
-            d['f3_out'] = K.pack_f16x3(w_out.float(), C, ntaps=1, order='natural')
-            d['qkv_l1'] = self._later(w_in.double().abs().sum(1), vector=True)
-            d['qkv_babs'] = self._later(mha.in_proj_bias.detach().double().abs(), vector=True)
-            d['gb'] = self._later_absmax(gn.weight, gn.bias)
-        return d
+        f3d = self.f3d and C % 16 == 0  # projection data gradients on f16x3 (per-image absmax bounds)
 
-    def _later(self, *vals, vector: bool = False):
-        """A host value computed on the device now and copied to the host with every other one of
-        this forward's packing bounds in ONE transfer (_resolve): one host sync per training forward
-        instead of one per GroupNorm / projection bound."""
-        slot = _Slot()
-        self._pending.append((slot, vals, vector))
-        return slot
+        def dgrad(w, C0: int):
+            return self._igemm(lambda: w.t(), C0, 1,
+                               f3=(lambda c: K.pack_f16x3(c.w, C0, ntaps=1, order='natural')) if f3d else None)
 
-    def _later_absmax(self, *tensors):
-        """A host tuple (max|t| for t in tensors), reduced with every other such request in one
-        multi-tensor launch (torch._foreach_norm, inf: exact) and copied with the rest in _resolve."""
-        slot = _Slot()
-        self._pending_max.append((slot, [t.detach() for t in tensors]))
-        return slot
+        ap = AttnTrain(C, mha.num_heads, gn, mha, self._igemm(lambda: w_in, C, 1), self._igemm(lambda: w_out, C, 1),
+                       dgrad(w_in, 3 * C), dgrad(w_out, C))
+        if self.f3 and C % 16 == 0:  # every forward launches these two
+            ap.proj_in.f3 = K.pack_f16x3(w_in.float(), C, ntaps=1, order='natural')
+            ap.proj_out.f3 = K.pack_f16x3(w_out.float(), C, ntaps=1, order='natural')
+        return ap
 
-    def _resolve(self, packs):
-        """Fill every slot _later / _later_absmax handed out and replace the slots inside the pack dicts."""
-        parts = [v.detach().reshape(-1).double() for _, vals, _ in self._pending for v in vals]
-        mx = [t for _, ts in self._pending_max for t in ts]
-        if mx:
-            parts.append(torch.stack(torch._foreach_norm(mx, float('inf'))).double())
-        if parts:
-            host = torch.cat(parts).cpu()
-            i = 0
-            for slot, vals, vector in self._pending:
-                if vector:
-                    n = vals[0].numel()
-                    slot.value = host[i:i + n]
-                    i += n
-                else:
-                    slot.value = tuple(float(host[i + j]) for j in range(len(vals)))
-                    i += len(vals)
-            for slot, ts in self._pending_max:
-                slot.value = tuple(float(host[i + j]) for j in range(len(ts)))
-                i += len(ts)
-        self._pending = []
-        self._pending_max = []
-        for d in packs:
-            for k, v in list(d.items()):
-                if isinstance(v, _Slot):
-                    d[k] = v.value
+    def _pack_down(self, conv) -> ScaleTrain:
+        w = conv.weight.detach()
+        co, ci = w.shape[0], w.shape[1]
+        f3 = self.f3 and ci % 16 == 0 and co % 16 == 0 and K.x6_tile(co)[1] == 128
+        # f16x3 halo forms: the forward on the space-to-depth kernel, the data gradient (the ConvT of dY,
+        # in = Co, with the same weight) on the one-launch ConvT kernel
+        return ScaleTrain(
+            conv, self._igemm(lambda: pack_conv(w), ci, 16, f3s=(lambda c: K.pack_f16x3_s2d(c.w, ci)) if f3 else None),
+            ConvForms(parts=lambda c: self._parts(w, co),
+                      f3t=(lambda c: K.pack_f16x3_convT(w.float())) if self.f3d and f3 else None))
+
+    def _pack_up(self, conv) -> ScaleTrain:
+        wt = conv.weight.detach()  # [Cin][Cout][4][4]
+        ci, co = wt.shape[0], wt.shape[1]
+        f3 = self.f3 and ci % 16 == 0 and co % 16 == 0
+        return ScaleTrain(
+            conv, ConvForms(parts=lambda c: self._parts(wt, ci),
+                            f3t=(lambda c: K.pack_f16x3_convT(wt.float())) if f3 else None),
+            self._igemm(lambda: pack_conv(wt), co, 16, f3s=(lambda c: K.pack_f16x3_s2d(c.w, co))
+                        if self.f3d and f3 and K.x6_tile(ci)[1] == 128 else None))
 
     def _pack(self):
         m = self.model
         self.P = 0
-        self._pending = []
-        self._pending_max = []
 
         def stage(blk, n_res):
             res = []
             for i in range(n_res):
-                rp = self._pack_res(blk, i)
-                rp['off'] = self.P
-                self.P += rp['co']
-                res.append(rp)
+                res.append(self._pack_res(blk, i, self.P))
+                self.P += res[-1].co
             att = [self._pack_attn(blk, i) for i in range(len(blk.attentions))] if blk.use_attn else []
             return res, att
 
@@ -259,70 +348,51 @@ class TrainEngine:
             self.downs = [stage(blk, blk.num_layers) for blk in m.downs]
             self.mids = [stage(blk, blk.num_layers + 1) for blk in m.mids]
             self.ups = [stage(blk, blk.num_layers) for blk in m.ups]
-            self.down_pk = []
-            for blk in m.downs:
-                if blk.down_sample:
-                    w = blk.down_sample_conv.weight.detach()
-                    ci = w.shape[1]
-                    L = _Pack.lazy
-                    f3 = self.f3 and ci % 16 == 0 and w.shape[0] % 16 == 0 and K.x6_tile(w.shape[0])[1] == 128
-                    self.down_pk.append(_Pack(
-                        mod=blk.down_sample_conv, pk=L(lambda w=w, ci=ci: self._pk(pack_conv(w), ci, 16)),
-                        # dgrad: ConvT of dY (in = Co), its four parity re-layouts built only if used
-                        dT=L(lambda w=w: [(taps, self._pk(wp, w.shape[0], len(taps)))
-                                          for taps, wp in (pack_convT(w, py, px) for py, px in _PARITIES)]),
-                        # f16x3 halo forms: the forward on the space-to-depth kernel, the data gradient (the
-                        # ConvT of dY with the same weight) on the one-launch ConvT kernel
-                        f3=L(lambda w=w, ci=ci: K.pack_f16x3_s2d(pack_conv(w).float(), ci)) if f3 else None,
-                        f3T=L(lambda w=w: K.pack_f16x3_convT(w.float())) if self.f3d and f3 else None))
-                else:
-                    self.down_pk.append(None)
-            self.up_pk = []
-            for blk in m.ups:
-                if blk.up_sample:
-                    wt = blk.up_sample_conv.weight.detach()  # [Cin][Cout][4][4]
-                    ci = wt.shape[0]
-                    L = _Pack.lazy
-                    co = wt.shape[1]
-                    f3 = self.f3 and ci % 16 == 0 and co % 16 == 0
-                    self.up_pk.append(_Pack(
-                        mod=blk.up_sample_conv,
-                        fw=L(lambda wt=wt, ci=ci: [(taps, self._pk(wp, ci, len(taps)))
-                                                   for taps, wp in (pack_convT(wt, py, px) for py, px in _PARITIES)]),
-                        dT=L(lambda wt=wt, co=co: self._pk(pack_conv(wt), co, 16)),
-                        f3=L(lambda wt=wt: K.pack_f16x3_convT(wt.float())) if f3 else None,
-                        f3T=L(lambda wt=wt, co=co: K.pack_f16x3_s2d(pack_conv(wt).float(), co))
-                        if self.f3d and f3 and K.x6_tile(ci)[1] == 128 else None))
-                else:
-                    self.up_pk.append(None)
+            self.down_pk = [self._pack_down(blk.down_sample_conv) if blk.down_sample else None for blk in m.downs]
+            self.up_pk = [self._pack_up(blk.up_sample_conv) if blk.up_sample else None for blk in m.ups]
             tp = m.t_proj
-            self.tproj = [tp[0].weight.detach().float().contiguous(), tp[0].bias.detach().float().contiguous(),
-                          tp[2].weight.detach().float().contiguous(), tp[2].bias.detach().float().contiguous()]
-            rows = [rp for st in self.downs + self.mids + self.ups for rp in st[0]]
+            self.tproj = [_f32(p).contiguous() for p in (tp[0].weight, tp[0].bias, tp[2].weight, tp[2].bias)]
+            stages = self.downs + self.mids + self.ups
+            rows = [rp for st in stages for rp in st[0]]
             # every ResBlock's Winograd packs (forward and data-gradient forms; the weights change each
             # step) in one launch instead of one each (forms.pack_batch off: built lazily one by one)
             if forms.current().pack_batch:
-                reqs = [(rp, k, r) for rp in rows for k, r in rp.get('_wino_raw', {}).items()]
-                for (rp, k, _), pk in zip(reqs, K.pack_wino_raw_batch([r for _, _, r in reqs])):
-                    dict.__setitem__(rp, k, pk)
-            self._resolve(rows + [ap for st in self.downs + self.mids + self.ups for ap in st[1]])
-            self.temb_w = torch.cat([rp['temb'].weight.detach().float() for rp in rows], 0).contiguous()
-            self.temb_b = torch.cat([rp['temb'].bias.detach().float() for rp in rows], 0).contiguous()
+                reqs = [cr for rp in rows for cr in rp.wino_raw]
+                for (c, _), pk in zip(reqs, K.pack_wino_raw_batch([r for _, r in reqs])):
+                    c.wn = pk
+            # the f16x3 bounds: every layer's reduced on the device (the GroupNorm affines' max |.| in one
+            # multi-tensor launch; inf norm: exact), then ONE transfer, one host sync per training forward
+            f3a = [ap for st in stages for ap in st[1] if ap.proj_in.has('f3')]
+            gns = [g for rp in rows for g in (rp.gn1, rp.gn2)] + [ap.gn for ap in f3a]
+            vecs = [v for ap in f3a for v in (ap.mha.in_proj_weight.detach().double().abs().sum(1),
+                                              ap.mha.in_proj_bias.detach().double().abs())]
+            gmax = torch._foreach_norm([p.detach() for g in gns for p in (g.weight, g.bias)], float('inf'))
+            host = torch.cat(vecs + [torch.stack(gmax).double()]).cpu()
+            i = 0
+            for ap in f3a:
+                n = 3 * ap.C
+                ap.qkv_l1, ap.qkv_babs = host[i:i + n], host[i + n:i + 2 * n]
+                i += 2 * n
+            gb = [tuple(p) for p in host[i:].view(-1, 2).tolist()]
+            for k, rp in enumerate(rows):
+                rp.gb1, rp.gb2 = gb[2 * k], gb[2 * k + 1]
+            for ap, p in zip(f3a, gb[2 * len(rows):]):
+                ap.gb = p
+            self.temb_w = torch.cat([_f32(rp.temb.weight) for rp in rows], 0).contiguous()
+            self.temb_b = torch.cat([_f32(rp.temb.bias) for rp in rows], 0).contiguous()
             self.res_rows = rows
             co = m.conv_out.weight.detach()  # [NO][C][3][3]
             NO, C = co.shape[0], co.shape[1]
             # the 3-channel head on its fp32 VALU kernels (wc_head_conv forward, wc_head_wgrad /
             # wc_head_dgrad backward): an MFMA tile pads its 3 channels 20x (forms.train_smallconv off:
             # the generic implicit GEMMs, kept for A/B)
-            self.head_small = forms.current().train_smallconv and NO == 3 and C in (32, 64)
-            if self.head_small:
-                self.head_wp = K.pack_head(co)
-                self.head_T = None
+            if forms.current().train_smallconv and NO == 3 and C in (32, 64):
+                self.head = HeadTrain(True, co, wp=K.pack_head(co))
             else:
-                self.head_pk = self._pk(pack_conv(co), C, 9)
                 wt = torch.zeros((C, 32, 3, 3), dtype=torch.float32, device=self.device)
                 wt[:, :NO] = co.flip([2, 3]).transpose(0, 1)
-                self.head_T = self._pk(pack_conv(wt), 32, 9)  # dgrad over the 32-channel padded loss gradient
+                self.head = HeadTrain(False, co, fwd=self._igemm_now(pack_conv(co), C, 9),
+                                      dgrad=self._igemm_now(pack_conv(wt), 32, 9))
 
     # ------------------------------------------------------------------ helpers
     def _new(self, B, H, W, C) -> torch.Tensor:
@@ -425,9 +495,7 @@ class TrainEngine:
 
     def _forward(self, x: torch.Tensor, t) -> torch.Tensor:
         m = self.model
-        mc = m.model_config
         self._pack()
-        self.tape = []
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         B, _, S, S2 = x.shape
         tt = torch.as_tensor(t).long().reshape(-1).to(self.device)
@@ -435,10 +503,8 @@ class TrainEngine:
             tt = tt.expand(B).contiguous()
         if tt.numel() != B:
             raise RuntimeError(f'timestep tensor has {tt.numel()} entries for a batch of {B}')
-        self.tt = tt
-        self._raised: Dict[int, bool] = {}
+        tape = Tape(tt, self.P, self.tproj, self.temb_w, self.res_rows)
         temb = K.temb(tt, *self.tproj, self.temb_w, self.temb_b)  # (B, P)
-        self.x = x
         dc = m.down_channels
         L = len(dc) - 1
         sizes = [(S, S2)]
@@ -446,20 +512,19 @@ class TrainEngine:
             h, w = sizes[-1]
             sizes.append((h // 2, w // 2) if m.down_sample[i] else (h, w))
         U = [self._new(B, sizes[i][0], sizes[i][1], 2 * dc[i]) for i in range(L)]
-        self.U = U
         cur = View(U[0], dc[0], dc[0])
-        K.conv_in(x, m.conv_in.weight.detach().float().contiguous(), m.conv_in.bias.detach().float().contiguous(), cur)
-        self.tape.append(('conv_in', cur))
+        K.conv_in(x, _f32(m.conv_in.weight).contiguous(), _f32(m.conv_in.bias).contiguous(), cur)
+        tape.records.append(ConvInRec(x, cur))
 
         def block(X: View, tgt: View, rp, att, amx=None) -> View:
             """amx: float32[B] the final writer of tgt raises to its per-image max |value| (the bound a
             following down / up conv needs); left zero when that writer is not an f16x3 kernel."""
             if att is None:
-                self._res_fwd(X, tgt, rp, temb, amx)
+                self._res_fwd(tape, X, tgt, rp, temb, amx)
             else:
-                ypre = View.full(self._new_gn(B, X.H, X.W, rp['co']))
-                self._res_fwd(X, ypre, rp, temb)
-                self._attn_fwd(ypre, tgt, att, amx)
+                ypre = View.full(self._new_gn(B, X.H, X.W, rp.co))
+                self._res_fwd(tape, X, ypre, rp, temb)
+                self._attn_fwd(tape, ypre, tgt, att, amx)
             return tgt
 
         def new_amx():
@@ -469,30 +534,31 @@ class TrainEngine:
             """The producer-raised bound when it was raised (nonzero), else a pass over v."""
             if amx is None:
                 return None
-            return amx if self._raised.pop(id(amx), False) else K.absmax_images(v)
+            return amx if tape.raised.pop(id(amx), False) else K.absmax_images(v)
 
         for i in range(L):
             res, att = self.downs[i]
+            dp = self.down_pk[i]
             H, W = sizes[i]
             final = View(U[i + 1], dc[i + 1], dc[i + 1]) if i < L - 1 else View.full(
                 self._new(B, sizes[i + 1][0], sizes[i + 1][1], dc[i + 1]))
-            amx = new_amx() if self.down_pk[i] is not None else None
+            amx = new_amx() if dp is not None else None
             for li, rp in enumerate(res):
                 last = li == len(res) - 1
-                tgt = final if (last and self.down_pk[i] is None) else View.full(self._new_gn(B, H, W, rp['co']))
+                tgt = final if (last and dp is None) else View.full(self._new_gn(B, H, W, rp.co))
                 cur = block(cur, tgt, rp, att[li] if att else None, amx if last else None)
-            if self.down_pk[i] is not None:
-                dp = self.down_pk[i]
+            if dp is not None:
                 seg = Seg(cur, TAPS4S2, stride=2)
-                bd = dp['mod'].bias.detach().float().contiguous()
+                bd = _f32(dp.mod.bias).contiguous()
                 Hm, Wm = sizes[i + 1]
-                f3 = dp['f3'] is not None and K.conv4x4s2_f16x3_ok(seg, final.C, Hm, Wm)
+                f3s = dp.fwd.f3s if dp.fwd.has('f3s') else None  # packed here, also when the shape then declines it
+                f3 = f3s is not None and K.conv4x4s2_f16x3_ok(seg, final.C, Hm, Wm)
                 bcur = bound_of(cur, amx)  # the conv's A bound and the weight gradient's
                 if f3:
-                    K.conv4x4s2_f16x3(seg, dp['f3'], bd, final, Hm=Hm, Wm=Wm, a_bound=bcur)
+                    K.conv4x4s2_f16x3(seg, f3s, bd, final, Hm=Hm, Wm=Wm, a_bound=bcur)
                 else:
-                    self._conv([seg], dp['pk'], bd, final, Hm, Wm)
-                self.tape.append(('down', cur, final, dp, bcur))
+                    self._conv([seg], dp.fwd, bd, final, Hm, Wm)
+                tape.records.append(DownRec(cur, final, dp, bcur))
                 cur = final
 
         amx = None
@@ -504,31 +570,32 @@ class TrainEngine:
                 if last and self.up_pk[0] is None:
                     tgt = View(U[L - 1], 0, dc[L - 1])
                 else:
-                    tgt = View.full(self._new_gn(B, H, W, rp['co']))
+                    tgt = View.full(self._new_gn(B, H, W, rp.co))
                 if last and self.up_pk[0] is not None:
                     amx = new_amx()
-                self._res_fwd(cur, tgt, rp, temb, amx if last and li >= len(att) else None)
+                self._res_fwd(tape, cur, tgt, rp, temb, amx if last and li >= len(att) else None)
                 cur = tgt
                 if li < len(att):
-                    nxt = View.full(self._new_gn(B, H, W, rp['co']))
-                    self._attn_fwd(cur, nxt, att[li], amx if last else None)
+                    nxt = View.full(self._new_gn(B, H, W, rp.co))
+                    self._attn_fwd(tape, cur, nxt, att[li], amx if last else None)
                     cur = nxt
 
         for k, (res, att) in enumerate(self.ups):
             i = L - 1 - k
             H, W = sizes[i]
-            if self.up_pk[k] is not None:
-                up = self.up_pk[k]
+            up = self.up_pk[k]
+            if up is not None:
                 dst = View(U[i], 0, dc[i])
-                b = up['mod'].bias.detach().float().contiguous()
-                f3 = up['f3'] is not None and K.convT4x4s2_f16x3_ok(Seg(cur, [(0, 0)]), dst.C)
+                b = _f32(up.mod.bias).contiguous()
+                f3t = up.fwd.f3t if up.fwd.has('f3t') else None  # as f3s above
+                f3 = f3t is not None and K.convT4x4s2_f16x3_ok(Seg(cur, [(0, 0)]), dst.C)
                 bcur = bound_of(cur, amx)
                 if f3:
-                    K.convT4x4s2_f16x3(Seg(cur, [(0, 0)]), up['f3'], b, dst, a_bound=bcur)
+                    K.convT4x4s2_f16x3(Seg(cur, [(0, 0)]), f3t, b, dst, a_bound=bcur)
                 else:
-                    for (py, px), (taps, pk) in zip(_PARITIES, up['fw']):
-                        self._conv([Seg(cur, taps)], pk, b, dst, cur.H, cur.W, out_map=(2, 2, py, px))
-                self.tape.append(('up', cur, dst, up, bcur))
+                    for (py, px), (taps, c) in zip(_PARITIES, up.fwd.parts):
+                        self._conv([Seg(cur, taps)], c, b, dst, cur.H, cur.W, out_map=(2, 2, py, px))
+                tape.records.append(UpRec(cur, dst, up, bcur))
             else:
                 assert cur.t is U[i] and cur.c0 == 0, 'non-upsampling level must have been written in place'
             cur = View.full(U[i])
@@ -537,100 +604,89 @@ class TrainEngine:
             for li, rp in enumerate(res):
                 last = li == len(res) - 1
                 tgt = View(U[i - 1], 0, dc[i - 1]) if (last and next_in_place) else View.full(
-                    self._new_gn(B, H, W, rp['co']))
+                    self._new_gn(B, H, W, rp.co))
                 cur = block(cur, tgt, rp, att[li] if att else None, amx if last else None)
 
         # head: GN -> SiLU -> conv_out, NCHW output
-        gn = m.norm_out
-        sc, sh, a0, o0 = K.gn_stats_pair(cur, gn.weight.detach().float(), gn.bias.detach().float(),
-                                         part=getattr(cur, '_wc_gn_done', None))
-        out = torch.empty((B, mc.im_channels, S, S2), dtype=torch.float32, device=self.device)
-        if self.head_small:
-            K.head_conv(cur, sc, sh, self.head_wp, m.conv_out.bias.detach().float().contiguous(), out)
+        gn, hp = m.norm_out, self.head
+        sc, sh, a0, o0 = K.gn_stats_pair(cur, _f32(gn.weight), _f32(gn.bias), part=getattr(cur, '_wc_gn_done', None))
+        out = torch.empty((B, m.model_config.im_channels, S, S2), dtype=torch.float32, device=self.device)
+        if hp.small:
+            K.head_conv(cur, sc, sh, hp.wp, _f32(m.conv_out.bias).contiguous(), out)
         else:
-            self._conv([Seg(cur, TAPS3, scale=sc, shift=sh, silu=True)], self.head_pk,
-                       m.conv_out.bias.detach().float().contiguous(), None, S, S2, out_nchw=out)
-        self.tape.append(('head', cur, (sc, sh, a0, o0)))
-        self.last_tape = Tape(self)
-        self.tape = []
+            self._conv([Seg(cur, TAPS3, scale=sc, shift=sh, silu=True)], hp.fwd, _f32(m.conv_out.bias).contiguous(),
+                       None, S, S2, out_nchw=out)
+        tape.records.append(HeadRec(cur, (sc, sh, a0, o0), hp))
+        self.last_tape = tape
         return out
 
-    def _res_fwd(self, X: View, Y: View, rp, temb: torch.Tensor, amx: Optional[torch.Tensor] = None):
+    def _conv3_fwd(self, segs, c: ConvForms, bias, out: View, gb, kw: dict, **f3kw):
+        """A ResBlock 3x3 conv behind its GroupNorm (affine bounds gb): Winograd if packed and eligible, else
+        halo f16x3 if packed and eligible, else the implicit GEMM.  kw goes to every arm, f3kw to the f16x3
+        ones.  Returns (an f16x3 arm ran, out's GroupNorm partials if its epilogue wrote them)."""
+        H, W, co = out.H, out.W, out.C
+        wino = c.has('wn') and K.wino_eligible(segs, co, H, W)
+        if not wino and not (c.has('f3h') and K.x6_eligible(segs, co, H, W)):
+            self._conv(segs, c, bias, out, H, W, **kw)
+            return False, None
+        gp = K.gn_epilogue(out, co, H, W)
+        launch, w = (K.conv3x3_wino, c.wn) if wino else (K.conv3x3_f16x3, c.f3h)
+        launch(segs, w, bias, out, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*gb, H * W * segs[0].view.C // 8), gn=gp,
+               **kw, **f3kw)
+        return True, gp
+
+    def _res_fwd(self, tape: Tape, X: View, Y: View, rp: ResTrain, temb, amx: Optional[torch.Tensor] = None):
         B, H, W = X.B, X.H, X.W
-        g1, g2 = rp['gn1'], rp['gn2']
-        co = rp['co']
-        st1 = K.gn_stats_pair(X, g1.weight.detach().float(), g1.bias.detach().float(), bound=True,
+        co = rp.co
+        st1 = K.gn_stats_pair(X, _f32(rp.gn1.weight), _f32(rp.gn1.bias), bound=True,
                               part=getattr(X, '_wc_gn_done', None))
         h = View.full(self._new_gn(B, H, W, co))
-        seg1 = [Seg(X, TAPS3, scale=st1[0], shift=st1[1], silu=True)]
-        b1 = rp['conv1'].bias.detach().float().contiguous()
-        gp1 = None  # h's GroupNorm partials, when conv1's epilogue wrote them
-        if rp.has('wn_1') and K.wino_eligible(seg1, co, H, W):
-            gp1 = K.gn_epilogue(h, co, H, W)
-            K.conv3x3_wino(seg1, rp['wn_1'], b1, h, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*rp['gb1'], H * W * X.C // 8),
-                           temb=temb[:, rp['off']:], temb_ld=temb.shape[1], gn=gp1)
-        elif rp.has('f3_1') and K.x6_eligible(seg1, co, H, W):
-            gp1 = K.gn_epilogue(h, co, H, W)
-            K.conv3x3_f16x3(seg1, rp['f3_1'], b1, h, Hm=H, Wm=W,
-                            a_exp=K.f16x3_a_exp(*rp['gb1'], H * W * X.C // 8), temb=temb[:, rp['off']:],
-                            temb_ld=temb.shape[1], gn=gp1)
-        else:
-            self._conv(seg1, rp['pk1'], b1, h, H, W, temb=temb[:, rp['off']:], temb_ld=temb.shape[1])
-        st2 = K.gn_stats_pair(h, g2.weight.detach().float(), g2.bias.detach().float(), part=gp1)
-        seg2 = [Seg(h, TAPS3, scale=st2[0], shift=st2[1], silu=True), Seg(X, TAPS1, kbase=9 * co)]
-        gp2 = None  # Y's partials (an attention block's input): the next GroupNorm's statistics
-        if rp.has('wn_2') and K.wino_eligible(seg2, co, H, W):
-            gp2 = K.gn_epilogue(Y, co, H, W)
-            K.conv3x3_wino(seg2, rp['wn_2'], rp['b2'], Y, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*rp['gb2'], H * W * co // 8),
-                           a_bound=st1[4], absmax=amx, gn=gp2)
-            if amx is not None:
-                self._raised[id(amx)] = True
-        elif rp.has('f3_2') and K.x6_eligible(seg2, co, H, W):
-            # the residual segment (raw X) in fp16 under GN1's per-image bound of |X|
-            gp2 = K.gn_epilogue(Y, co, H, W)
-            K.conv3x3_f16x3(seg2, rp['f3_2'], rp['b2'], Y, Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*rp['gb2'], H * W * co // 8),
-                            a_bound=st1[4], absmax=amx, gn=gp2)
-            if amx is not None:
-                self._raised[id(amx)] = True
-        else:
-            self._conv(seg2, rp['pk2'], rp['b2'], Y, H, W)
+        # gp1: h's GroupNorm partials, when conv1's epilogue wrote them
+        _, gp1 = self._conv3_fwd([Seg(X, TAPS3, scale=st1[0], shift=st1[1], silu=True)], rp.conv1,
+                                 _f32(rp.mod1.bias).contiguous(), h, rp.gb1,
+                                 dict(temb=temb[:, rp.off:], temb_ld=temb.shape[1]))
+        st2 = K.gn_stats_pair(h, _f32(rp.gn2.weight), _f32(rp.gn2.bias), part=gp1)
+        # the residual segment (raw X) in fp16 under GN1's per-image bound of |X|; gp2: Y's partials (an
+        # attention block's input), the next GroupNorm's statistics
+        f3, gp2 = self._conv3_fwd([Seg(h, TAPS3, scale=st2[0], shift=st2[1], silu=True), Seg(X, TAPS1, kbase=9 * co)],
+                                  rp.conv2, rp.b2, Y, rp.gb2, {}, a_bound=st1[4], absmax=amx)
+        if f3 and amx is not None:
+            tape.raised[id(amx)] = True
         if gp2 is not None:
             Y._wc_gn_done = gp2
-        self.tape.append(('res', X, h, Y, rp, st1[:4], st2, st1[4]))
+        tape.records.append(ResRec(X, h, Y, rp, st1, st2))
 
-    def _attn_fwd(self, Ypre: View, Yout: View, ap, amx: Optional[torch.Tensor] = None):
+    def _attn_fwd(self, tape: Tape, Ypre: View, Yout: View, ap: AttnTrain, amx: Optional[torch.Tensor] = None):
         B, H, W, C = Ypre.B, Ypre.H, Ypre.W, Ypre.C
         N = H * W
-        gn, mha = ap['gn'], ap['mha']
-        st = K.gn_stats_pair(Ypre, gn.weight.detach().float(), gn.bias.detach().float(),
-                             part=getattr(Ypre, '_wc_gn_done', None))
+        gn, mha = ap.gn, ap.mha
+        st = K.gn_stats_pair(Ypre, _f32(gn.weight), _f32(gn.bias), part=getattr(Ypre, '_wc_gn_done', None))
         qkv = self._new(B, H, W, 3 * C)
         seg = [Seg(Ypre, TAPS1, scale=st[0], shift=st[1], silu=False)]
-        b_in = mha.in_proj_bias.detach().float().contiguous()
+        b_in = _f32(mha.in_proj_bias).contiguous()
         o = self._new(B, H, W, C)
-        lse = torch.empty((B, ap['heads'], N), dtype=torch.float32, device=self.device)
-        b_out = mha.out_proj.bias.detach().float().contiguous()
-        if ap['f3_in'] is not None:
+        lse = torch.empty((B, ap.heads, N), dtype=torch.float32, device=self.device)
+        b_out = _f32(mha.out_proj.bias).contiguous()
+        attn = (qkv.view(B * N, 3 * C), o.view(B * N, C), lse, B, N, C, ap.heads)
+        if ap.proj_in.has('f3'):
             # in_proj under the GN bound; attention on f16x3 under the in-projection row-norm bounds
             # of Q, K, V (as the sampler); out_proj: |O| <= max|V| (a convex combination of V rows)
             ng = N * C // 8
-            K.conv_igemm_f16x3(seg, ap['f3_in'], b_in, View.full(qkv), Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*ap['gb'], ng))
-            exps = K.attention_exps_from_norms(ap['qkv_l1'], ap['qkv_babs'], ap['gb'][0], ap['gb'][1], ng)
-            K.attention_fwd_lse(qkv.view(B * N, 3 * C), o.view(B * N, C), lse, B, N, C, ap['heads'],
-                                precision='f16x3', exps=exps)
+            K.conv_igemm_f16x3(seg, ap.proj_in.f3, b_in, View.full(qkv), Hm=H, Wm=W, a_exp=K.f16x3_a_exp(*ap.gb, ng))
+            exps = K.attention_exps_from_norms(ap.qkv_l1, ap.qkv_babs, ap.gb[0], ap.gb[1], ng)
+            K.attention_fwd_lse(*attn, precision='f16x3', exps=exps)
             gpo = K.gn_epilogue(Yout, C, H, W, K.igemm_bm(C))
-            K.conv_igemm_f16x3([Seg(View.full(o), TAPS1)], ap['f3_out'], b_out, Yout, Hm=H, Wm=W, a_exp=exps[2],
+            K.conv_igemm_f16x3([Seg(View.full(o), TAPS1)], ap.proj_out.f3, b_out, Yout, Hm=H, Wm=W, a_exp=exps[2],
                                res=Ypre, absmax=amx, gn=gpo)
             if amx is not None:
-                self._raised[id(amx)] = True
+                tape.raised[id(amx)] = True
             if gpo is not None:
                 Yout._wc_gn_done = gpo
         else:
-            self._conv(seg, ap['pk_in'], b_in, View.full(qkv), H, W)
-            K.attention_fwd_lse(qkv.view(B * N, 3 * C), o.view(B * N, C), lse, B, N, C, ap['heads'],
-                                precision=self.precision)
-            self._conv([Seg(View.full(o), TAPS1)], ap['pk_out'], b_out, Yout, H, W, res=Ypre)
-        self.tape.append(('attn', Ypre, Yout, qkv, o, lse, st, ap))
+            self._conv(seg, ap.proj_in, b_in, View.full(qkv), H, W)
+            K.attention_fwd_lse(*attn, precision=self.precision)
+            self._conv([Seg(View.full(o), TAPS1)], ap.proj_out, b_out, Yout, H, W, res=Ypre)
+        tape.records.append(AttnRec(Ypre, Yout, qkv, o, lse, st, ap))
 
     # ------------------------------------------------------------------ backward
     def backward(self, gout: torch.Tensor, tape: Optional[Tape] = None) -> Dict[int, torch.Tensor]:
@@ -646,43 +702,32 @@ class TrainEngine:
         if tape is None or tape.consumed:
             raise RuntimeError('Unet training backward: this forward\'s saved activations were already consumed '
                                'by an earlier backward (retain_graph / a second backward is not supported)')
-        for f in Tape._FIELDS[1:]:
-            setattr(self, f, getattr(tape, f))
-        records = tape.records
+        records, tape.records = tape.records, []
         tape.consumed = True
-        tape.records = []
         if self.last_tape is tape:
             self.last_tape = None
-        m = self.model
-        self.gmap: Dict[int, Tuple[torch.Tensor, int]] = {}
-        self.gfresh = set()  # gradient tensors allocated but not yet written (_gview)
-        self.gbnd: Dict[int, torch.Tensor] = {}
-        self.pgrads: Dict[int, torch.Tensor] = {}
-        self.pflat_off: Dict[int, Tuple[int, int]] = {}
+        # this backward's gradient bookkeeping (_gview .. _pgrad), cleared again below: gmap {id(forward tensor):
+        # (gradient tensor, channel offset)}, gfresh the gradient tensors allocated but not yet written, gbnd
+        # {id(gradient tensor): its bound}, pgrads {id(param): grad}, pflat_off {id(param): (offset, numel) in pflat}
+        self.gmap, self.gfresh, self.gbnd, self.pgrads, self.pflat_off, self.keep = {}, set(), {}, {}, {}, []
         tot = 0
-        for prm in m.parameters():
+        for prm in self.model.parameters():
             self.pflat_off[id(prm)] = (tot, prm.numel())
             tot += (prm.numel() + 63) // 64 * 64  # 256-byte aligned views
         self.pflat = torch.zeros(tot, dtype=torch.float32, device=self.device)
-        self.keep = []
-        B = gout.shape[0]
-        self.dproj = torch.zeros((B, self.P), dtype=torch.float32, device=self.device)
+        self.dproj = torch.zeros((gout.shape[0], tape.P), dtype=torch.float32, device=self.device)
         gout = gout.to(self.device, torch.float32).contiguous()
         K.bsum_defer()  # the ~200 per-layer dgamma / dbeta / bias sums go out in one launch at the end
         try:
-            for rec in reversed(records):
-                getattr(self, '_bwd_' + rec[0])(rec, gout)
+            self._bwd_head(records[-1], gout)
+            for rec in reversed(records[:-1]):
+                self._BWD[type(rec)](self, rec)
             del records
-            self._temb_bwd()
+            self._temb_bwd(tape)
         finally:
             K.bsum_flush()
-        self.gmap = {}
-        self.gfresh = set()
-        self.gbnd = {}
-        self.keep = []
-        for f in Tape._FIELDS[1:]:  # the tape's tensors die with it, not with the engine
-            setattr(self, f, None)
-        grads, self.pgrads, self.pflat = self.pgrads, {}, None
+        grads, self.pgrads = self.pgrads, {}
+        self.gmap, self.gfresh, self.gbnd, self.keep, self.pflat, self.dproj = {}, set(), {}, [], None, None
         return grads
 
     @staticmethod
@@ -690,6 +735,22 @@ class TrainEngine:
         """The 3x3 data gradient of g (n_out output channels) fits the halo f16x3 kernel."""
         return K.x6_eligible([Seg(g, TAPS3)], n_out, g.H, g.W) and g.C % 4 == 0 and g.ldc % 4 == 0 \
             and g.ptr % 16 == 0
+
+    def _dgrad3(self, g: View, c: ConvForms, f3: bool, bound, dz: View, gnb_sums: Callable):
+        """dz = the 3x3 data gradient of g through c.  f3 (the f16x3 pack exists and _dgrad3_ok; bound: the per-image
+        max |g|): Winograd if packed and eligible, else the halo kernel; otherwise the implicit GEMM.  The Winograd
+        arm forms the next GroupNorm backward's sums, gnb_sums(), in its epilogue (no pass over dz) and returns them."""
+        seg = [Seg(g, TAPS3)]
+        H, W = g.H, g.W
+        if not f3:
+            self._conv(seg, c, None, dz, H, W)
+        elif c.has('wn') and K.wino_eligible(seg, dz.C, H, W):
+            pre = gnb_sums() if forms.current().train_gnb_epilogue else None
+            K.conv3x3_wino(seg, c.wn, None, dz, Hm=H, Wm=W, a_exp=60, a_bound=bound, gnb=pre)
+            return pre
+        else:
+            K.conv3x3_f16x3(seg, c.f3h, None, dz, Hm=H, Wm=W, a_exp=60, a_bound=bound)
+        return None
 
     def _wgrad(self, g: View, segs, dw0, s0, f3=None, **kw):
         """Weight gradient on bf16x6 (precision bf16x6) or fp32 MFMA; f3 = (x_exp, per-image max |g|):
@@ -702,181 +763,152 @@ class TrainEngine:
             K.bsum(sums, 0, self._pgrad(p), accumulate=True)
         return sums
 
-    def _bwd_head(self, rec, gout):
+    def _bwd_head(self, rec: HeadRec, gout: torch.Tensor):
         m = self.model
-        _, cur, (sc, sh, a0, o0) = rec
+        cur, (sc, sh, a0, o0), hp = rec
         B, NO, S, S2 = gout.shape
         C = cur.C
-        if self.head_small:
+        if hp.small:
             g = gout.contiguous().float()
             K.head_wgrad(cur, sc, sh, g, self._pgrad(m.conv_out.weight))
             self._pgrad(m.conv_out.bias).copy_(g.sum((0, 2, 3)))
             dz = View.full(self._new(B, S, S2, C))
-            K.head_dgrad(g, m.conv_out.weight, dz)
-            gn = m.norm_out
-            gcur, ow = self._grad_w(cur)
-            K.gn_backward(dz, cur, a0, o0, gn.weight.detach().float(), gn.bias.detach().float(), True, gcur,
-                          dgamma=self._pgrad(gn.weight), dbeta=self._pgrad(gn.bias), accumulate=not ow,
-                          absmax=self._gb(cur))
-            return
-        g32 = K.nchw_to_nhwc(gout, 32)
-        g4 = View(g32, 0, 4)
-        wtmp = torch.zeros((4, C, 3, 3), dtype=torch.float32, device=self.device)
-        self._wgrad(g4, [Seg(cur, TAPS3, scale=sc, shift=sh, silu=True)], wtmp, (C * 9, 9, 1))
-        self._pgrad(m.conv_out.weight).copy_(wtmp[:NO])
-        btmp = torch.zeros(4, dtype=torch.float32, device=self.device)
-        K.bsum(K.channel_sums(g4), 0, btmp, now=True)  # read by the copy below
-        self._pgrad(m.conv_out.bias).copy_(btmp[:NO])
-        dz = View.full(self._new(B, S, S2, C))
-        self._conv([Seg(View.full(g32), TAPS3)], self.head_T, None, dz, S, S2)
+            K.head_dgrad(g, hp.w, dz)
+        else:
+            g32 = K.nchw_to_nhwc(gout, 32)
+            g4 = View(g32, 0, 4)
+            wtmp = torch.zeros((4, C, 3, 3), dtype=torch.float32, device=self.device)
+            self._wgrad(g4, [Seg(cur, TAPS3, scale=sc, shift=sh, silu=True)], wtmp, (C * 9, 9, 1))
+            self._pgrad(m.conv_out.weight).copy_(wtmp[:NO])
+            btmp = torch.zeros(4, dtype=torch.float32, device=self.device)
+            K.bsum(K.channel_sums(g4), 0, btmp, now=True)  # read by the copy below
+            self._pgrad(m.conv_out.bias).copy_(btmp[:NO])
+            dz = View.full(self._new(B, S, S2, C))
+            self._conv([Seg(View.full(g32), TAPS3)], hp.dgrad, None, dz, S, S2)
         gn = m.norm_out
         gcur, ow = self._grad_w(cur)
-        K.gn_backward(dz, cur, a0, o0, gn.weight.detach().float(), gn.bias.detach().float(), True, gcur,
-                      dgamma=self._pgrad(gn.weight), dbeta=self._pgrad(gn.bias), accumulate=not ow,
-                      absmax=self._gb(cur))
+        K.gn_backward(dz, cur, a0, o0, _f32(gn.weight), _f32(gn.bias), True, gcur, dgamma=self._pgrad(gn.weight),
+                      dbeta=self._pgrad(gn.bias), accumulate=not ow, absmax=self._gb(cur))
 
-    def _bwd_res(self, rec, gout):
-        _, X, h, Y, rp, st1, st2, bXf = rec  # bXf: GN1's per-image bound of |X| (the forward's)
+    def _bwd_res(self, rec: ResRec):
+        X, h, Y, rp, st1, st2 = rec
         B, H, W = X.B, X.H, X.W
-        ci, co = rp['ci'], rp['co']
+        ci, co = rp.ci, rp.co
         gY = self._grad(Y)
         gX = self._gview(X)  # written first by the residual conv's data gradient below
-        self._bias_grad(gY, rp['conv2'].bias, rp['resc'].bias)
+        self._bias_grad(gY, rp.mod2.bias, rp.modr.bias)
         # per-image max |gY|: the range bound of the f16x3 data gradients and weight gradient
-        f3Y = rp.has('f3_2T') and self._dgrad3_ok(gY, co)
+        f3Y = rp.d2.has('f3h') and self._dgrad3_ok(gY, co)
         bY = self._bound(gY, self._gb(Y)) if f3Y else None
         bX = self._gb(X)
         self._wgrad(gY, [Seg(h, TAPS3, scale=st2[0], shift=st2[1], silu=True), Seg(X, TAPS1, kbase=9 * co)],
-                    self._pgrad(rp['conv2'].weight), (co * 9, 9, 1), dw1=self._pgrad(rp['resc'].weight), s1=ci,
-                    f3=K.F3Bounds(bY, K.f16x3_a_exp(*rp['gb2'], H * W * co // 8), None, bXf) if f3Y else None)
+                    self._pgrad(rp.mod2.weight), (co * 9, 9, 1), dw1=self._pgrad(rp.modr.weight), s1=ci,
+                    f3=K.F3Bounds(bY, K.f16x3_a_exp(*rp.gb2, H * W * co // 8), None, st1[4]) if f3Y else None)
         dz2 = View.full(self._new(B, H, W, co))
-        g2 = rp['gn2']
-        ga2, be2 = g2.weight.detach().float(), g2.bias.detach().float()
+        ga2, be2 = _f32(rp.gn2.weight), _f32(rp.gn2.bias)
         # dh's per-(image, channel) sums (conv1's bias / time-embedding gradients) in closed form from the
         # GN backward's own sums (forms.train_dh_sums off: a channel_sums pass over dh)
         dh_sums = forms.current().train_dh_sums
-        pre2 = None
-        if f3Y:
-            if rp.has('wn_2T') and K.wino_eligible([Seg(gY, TAPS3)], co, H, W):
-                # GN2's backward sums of dz2 formed in the data-gradient conv's epilogue (no pass over dz2)
-                if forms.current().train_gnb_epilogue:
-                    pre2 = K.GnbSums.make(h, st2[2], st2[3], ga2, be2, True, dx_sums=dh_sums)
-                K.conv3x3_wino([Seg(gY, TAPS3)], rp['wn_2T'], None, dz2, Hm=H, Wm=W, a_exp=60, a_bound=bY, gnb=pre2)
-            else:
-                K.conv3x3_f16x3([Seg(gY, TAPS3)], rp['f3_2T'], None, dz2, Hm=H, Wm=W, a_exp=60, a_bound=bY)
-            gX, ow = self._grad_w(X)
-            rX = None if ow else gX
-            if (H * W) % (256 if ci <= 64 else 128) == 0 and co % 16 == 0:  # one-image M tiles (per-image bound)
-                K.conv_igemm_f16x3([Seg(gY, TAPS1)], rp['f3_rT'], None, gX, Hm=H, Wm=W, a_exp=60, a_bound=bY, res=rX,
-                                   absmax=bX)
-            else:
-                self._conv([Seg(gY, TAPS1)], rp['pkrT'], None, gX, H, W, res=rX, absmax=bX)
+        pre2 = self._dgrad3(gY, rp.d2, f3Y, bY, dz2,
+                            lambda: K.GnbSums.make(h, st2[2], st2[3], ga2, be2, True, dx_sums=dh_sums))
+        gX, ow = self._grad_w(X)
+        rX = None if ow else gX
+        if f3Y and _one_image_tiles(H, W, ci) and co % 16 == 0:  # per-image bound
+            K.conv_igemm_f16x3([Seg(gY, TAPS1)], rp.dr.f3, None, gX, Hm=H, Wm=W, a_exp=60, a_bound=bY, res=rX,
+                               absmax=bX)
         else:
-            self._conv([Seg(gY, TAPS3)], rp['pk2T'], None, dz2, H, W)
-            gX, ow = self._grad_w(X)
-            self._conv([Seg(gY, TAPS1)], rp['pkrT'], None, gX, H, W, res=None if ow else gX, absmax=bX)
+            self._conv([Seg(gY, TAPS1)], rp.dr, None, gX, H, W, res=rX, absmax=bX)
         dh = View.full(self._new(B, H, W, co))
         bdh = self._zrow(B) if self.f3d else None
-        sums = K.gn_backward(dz2, h, st2[2], st2[3], ga2, be2, True, dh, dgamma=self._pgrad(g2.weight),
-                             dbeta=self._pgrad(g2.bias), accumulate=False, absmax=bdh, dx_sums=dh_sums, pre=pre2)
+        sums = K.gn_backward(dz2, h, st2[2], st2[3], ga2, be2, True, dh, dgamma=self._pgrad(rp.gn2.weight),
+                             dbeta=self._pgrad(rp.gn2.bias), accumulate=False, absmax=bdh, dx_sums=dh_sums, pre=pre2)
         if sums is None:
             sums = K.channel_sums(dh)
-        K.bsum(sums, 0, self._pgrad(rp['conv1'].bias), accumulate=True)
-        self.dproj[:, rp['off']:rp['off'] + co].copy_(sums[:, :, 0])
-        f3h = rp.has('f3_1T') and self._dgrad3_ok(dh, ci)
+        K.bsum(sums, 0, self._pgrad(rp.mod1.bias), accumulate=True)
+        self.dproj[:, rp.off:rp.off + co].copy_(sums[:, :, 0])
+        f3h = rp.d1.has('f3h') and self._dgrad3_ok(dh, ci)
         bh = self._bound(dh, bdh) if f3h else None
-        self._wgrad(dh, [Seg(X, TAPS3, scale=st1[0], shift=st1[1], silu=True)], self._pgrad(rp['conv1'].weight),
-                    (ci * 9, 9, 1), f3=K.F3Bounds(bh, K.f16x3_a_exp(*rp['gb1'], H * W * ci // 8)) if f3h else None)
+        self._wgrad(dh, [Seg(X, TAPS3, scale=st1[0], shift=st1[1], silu=True)], self._pgrad(rp.mod1.weight),
+                    (ci * 9, 9, 1), f3=K.F3Bounds(bh, K.f16x3_a_exp(*rp.gb1, H * W * ci // 8)) if f3h else None)
         dz1 = View.full(self._new(B, H, W, ci))
-        g1 = rp['gn1']
-        ga1, be1 = g1.weight.detach().float(), g1.bias.detach().float()
-        pre1 = None
-        if f3h:
-            if rp.has('wn_1T') and K.wino_eligible([Seg(dh, TAPS3)], ci, H, W):
-                if forms.current().train_gnb_epilogue:
-                    pre1 = K.GnbSums.make(X, st1[2], st1[3], ga1, be1, True)
-                K.conv3x3_wino([Seg(dh, TAPS3)], rp['wn_1T'], None, dz1, Hm=H, Wm=W, a_exp=60, a_bound=bh, gnb=pre1)
-            else:
-                K.conv3x3_f16x3([Seg(dh, TAPS3)], rp['f3_1T'], None, dz1, Hm=H, Wm=W, a_exp=60, a_bound=bh)
-        else:
-            self._conv([Seg(dh, TAPS3)], rp['pk1T'], None, dz1, H, W)
-        K.gn_backward(dz1, X, st1[2], st1[3], ga1, be1, True, gX, dgamma=self._pgrad(g1.weight),
-                      dbeta=self._pgrad(g1.bias), accumulate=True, absmax=bX, pre=pre1)
+        ga1, be1 = _f32(rp.gn1.weight), _f32(rp.gn1.bias)
+        pre1 = self._dgrad3(dh, rp.d1, f3h, bh, dz1, lambda: K.GnbSums.make(X, st1[2], st1[3], ga1, be1, True))
+        K.gn_backward(dz1, X, st1[2], st1[3], ga1, be1, True, gX, dgamma=self._pgrad(rp.gn1.weight),
+                      dbeta=self._pgrad(rp.gn1.bias), accumulate=True, absmax=bX, pre=pre1)
 
-    def _bwd_attn(self, rec, gout):
-        _, Ypre, Yout, qkv, o, lse, st, ap = rec
+    def _bwd_attn(self, rec: AttnRec):
+        Ypre, Yout, qkv, o, lse, st, ap = rec
         B, H, W, C = Ypre.B, Ypre.H, Ypre.W, Ypre.C
         N = H * W
-        mha, gn = ap['mha'], ap['gn']
+        mha, gn = ap.mha, ap.gn
         gY = self._grad(Yout)
         self._bias_grad(gY, mha.out_proj.bias)
-        f3a = self.f3d and ap['f3_in'] is not None
+        f3a = self.f3d and ap.proj_in.has('f3')
         # the forward's Q / K / V exponents (|O| <= max|V|: O shares V's)
-        exps = K.attention_exps_from_norms(ap['qkv_l1'], ap['qkv_babs'], ap['gb'][0], ap['gb'][1], N * C // 8) \
-            if f3a else None
+        exps = K.attention_exps_from_norms(ap.qkv_l1, ap.qkv_babs, ap.gb[0], ap.gb[1], N * C // 8) if f3a else None
         bgY = self._bound(gY, self._gb(Yout)) if self.f3d else None
         self._wgrad(gY, [Seg(View.full(o), TAPS1)], self._pgrad(mha.out_proj.weight), (C, 1, 0),
                     f3=K.F3Bounds(bgY, exps[2]) if f3a else None)
         do = self._new(B, H, W, C)
         bdo = self._zrow(B) if self.f3d else None
-        f3p = 'f3_outT' in ap and (H * W) % (256 if C <= 64 else 128) == 0
+        f3p = ap.d_out.has('f3') and _one_image_tiles(H, W, C)
         if f3p:
-            K.conv_igemm_f16x3([Seg(gY, TAPS1)], ap['f3_outT'], None, View.full(do), Hm=H, Wm=W, a_exp=60,
+            K.conv_igemm_f16x3([Seg(gY, TAPS1)], ap.d_out.f3, None, View.full(do), Hm=H, Wm=W, a_exp=60,
                                a_bound=bgY, absmax=bdo)
         else:
-            self._conv([Seg(gY, TAPS1)], ap['pk_outT'], None, View.full(do), H, W, absmax=bdo)
+            self._conv([Seg(gY, TAPS1)], ap.d_out, None, View.full(do), H, W, absmax=bdo)
         dqkv = self._new(B, H, W, 3 * C)
         bgq = None
+        args = (*(t.view(B * N, -1) for t in (qkv, o, do)), lse, dqkv.view(B * N, 3 * C), B, N, C, ap.heads)
         if f3a:
             # f16x3 under the forward's Q / K / V exponents and the per-image max |dO|; the kernels raise
             # the per-image max |dqkv| as they write it (head dims 32 / 64 / 128)
             bgq = self._zrow(B)
-            if not K.attention_bwd(qkv.view(B * N, 3 * C), o.view(B * N, C), do.view(B * N, C), lse,
-                                   dqkv.view(B * N, 3 * C), B, N, C, ap['heads'], precision='f16x3', exps=exps,
-                                   dout_bound=self._bound(View.full(do), bdo), dqkv_absmax=bgq):
+            if not K.attention_bwd(*args, precision='f16x3', exps=exps, dout_bound=self._bound(View.full(do), bdo),
+                                   dqkv_absmax=bgq):
                 bgq = None
         else:
-            K.attention_bwd(qkv.view(B * N, 3 * C), o.view(B * N, C), do.view(B * N, C), lse, dqkv.view(B * N, 3 * C),
-                            B, N, C, ap['heads'], precision=self.precision)
+            K.attention_bwd(*args, precision=self.precision)
         gq = View.full(dqkv)
         self._bias_grad(gq, mha.in_proj_bias)
         if f3a or f3p:
             bgq = self._bound(gq, bgq) if bgq is not None else K.absmax_images(gq)
         self._wgrad(gq, [Seg(Ypre, TAPS1, scale=st[0], shift=st[1], silu=False)], self._pgrad(mha.in_proj_weight),
-                    (C, 1, 0), f3=K.F3Bounds(bgq, K.f16x3_a_exp(*ap['gb'], N * C // 8)) if f3a else None)
+                    (C, 1, 0), f3=K.F3Bounds(bgq, K.f16x3_a_exp(*ap.gb, N * C // 8)) if f3a else None)
         da = View.full(self._new(B, H, W, C))
         if f3p:
-            K.conv_igemm_f16x3([Seg(gq, TAPS1)], ap['f3_inT'], None, da, Hm=H, Wm=W, a_exp=60, a_bound=bgq)
+            K.conv_igemm_f16x3([Seg(gq, TAPS1)], ap.d_in.f3, None, da, Hm=H, Wm=W, a_exp=60, a_bound=bgq)
         else:
-            self._conv([Seg(gq, TAPS1)], ap['pk_inT'], None, da, H, W)
+            self._conv([Seg(gq, TAPS1)], ap.d_in, None, da, H, W)
         # Yout = Ypre + out_proj(...): Ypre's gradient is Yout's plus the GroupNorm path
         self._alias_grad(Ypre.t, Yout)
-        K.gn_backward(da, Ypre, st[2], st[3], gn.weight.detach().float(), gn.bias.detach().float(), False,
-                      self._grad(Ypre), dgamma=self._pgrad(gn.weight), dbeta=self._pgrad(gn.bias), accumulate=True,
+        K.gn_backward(da, Ypre, st[2], st[3], _f32(gn.weight), _f32(gn.bias), False, self._grad(Ypre),
+                      dgamma=self._pgrad(gn.weight), dbeta=self._pgrad(gn.bias), accumulate=True,
                       absmax=self._gb(Ypre))
 
-    def _bwd_down(self, rec, gout):
-        _, cur, final, dp, bcur = rec  # bcur: the forward's per-image max |cur|
+    def _bwd_down(self, rec: DownRec):
+        cur, final, dp, bcur = rec  # bcur: the forward's per-image max |cur|
         gF = self._grad(final)
-        w = dp['mod'].weight
-        self._bias_grad(gF, dp['mod'].bias)
+        w = dp.mod.weight
+        self._bias_grad(gF, dp.mod.bias)
         bgF = self._bound(gF, self._gb(final)) if self.f3d else None
         self._wgrad(gF, [Seg(cur, TAPS4S2, stride=2)], self._pgrad(w), (w.shape[1] * 16, 16, 1),
                     f3=K.F3Bounds(bgF, 60, bcur) if bgF is not None and bcur is not None else None)
         gc, ow = self._grad_w(cur)  # the four output parities together cover every pixel
         rc = None if ow else gc
-        if dp['f3T'] is not None and K.convT4x4s2_f16x3_ok(Seg(gF, [(0, 0)]), gc.C) and gF.ptr % 16 == 0:
+        f3t = dp.dgrad.f3t if dp.dgrad.has('f3t') else None  # packed here, also when the shape then declines it
+        if f3t is not None and K.convT4x4s2_f16x3_ok(Seg(gF, [(0, 0)]), gc.C) and gF.ptr % 16 == 0:
             # the ConvT of dY (same weight) in one launch on f16x3 under dY's tracked bound
-            K.convT4x4s2_f16x3(Seg(gF, [(0, 0)]), dp['f3T'], None, gc, a_bound=bgF, res=rc, absmax=self._gb(cur))
+            K.convT4x4s2_f16x3(Seg(gF, [(0, 0)]), f3t, None, gc, a_bound=bgF, res=rc, absmax=self._gb(cur))
             return
-        for (py, px), (taps, pk) in zip(_PARITIES, dp['dT']):
-            self._conv([Seg(gF, taps)], pk, None, gc, gF.H, gF.W, out_map=(2, 2, py, px), res=rc, absmax=self._gb(cur))
+        for (py, px), (taps, c) in zip(_PARITIES, dp.dgrad.parts):
+            self._conv([Seg(gF, taps)], c, None, gc, gF.H, gF.W, out_map=(2, 2, py, px), res=rc, absmax=self._gb(cur))
 
-    def _bwd_up(self, rec, gout):
-        _, cur, dst, up, bcur = rec
+    def _bwd_up(self, rec: UpRec):
+        cur, dst, up, bcur = rec
         gD = self._grad(dst)
-        wt = up['mod'].weight  # [Cin][Cout][4][4]
-        self._bias_grad(gD, up['mod'].bias)
+        wt = up.mod.weight  # [Cin][Cout][4][4]
+        self._bias_grad(gD, up.mod.bias)
         # dW[ci][co][ky][kx] = sum_pixels x[ci] * dY[co] at (2y - 1 + ky, 2x - 1 + kx): the 4x4/s2 tap
         # grid over dY with x in the gradient role
         bgD = self._bound(gD, self._gb(dst)) if self.f3d else None
@@ -885,31 +917,34 @@ class TrainEngine:
         seg = Seg(gD, TAPS4S2, stride=2)
         gc, ow = self._grad_w(cur)
         rc = None if ow else gc
-        if up['f3T'] is not None and K.conv4x4s2_f16x3_ok(seg, gc.C, cur.H, cur.W) and gD.ptr % 16 == 0:
+        f3s = up.dgrad.f3s if up.dgrad.has('f3s') else None  # as f3t in _bwd_down
+        if f3s is not None and K.conv4x4s2_f16x3_ok(seg, gc.C, cur.H, cur.W) and gD.ptr % 16 == 0:
             # the 4x4/s2 conv of dY on the space-to-depth halo kernel, f16x3 under dY's tracked bound
-            K.conv4x4s2_f16x3(seg, up['f3T'], None, gc, Hm=cur.H, Wm=cur.W, a_bound=bgD, res=rc, absmax=self._gb(cur))
+            K.conv4x4s2_f16x3(seg, f3s, None, gc, Hm=cur.H, Wm=cur.W, a_bound=bgD, res=rc, absmax=self._gb(cur))
             return
-        self._conv([seg], up['dT'], None, gc, cur.H, cur.W, res=rc, absmax=self._gb(cur))
+        self._conv([seg], up.dgrad, None, gc, cur.H, cur.W, res=rc, absmax=self._gb(cur))
 
-    def _bwd_conv_in(self, rec, gout):
+    def _bwd_conv_in(self, rec: ConvInRec):
         m = self.model
-        _, cur = rec
+        x, cur = rec
         g = self._grad(cur)
         self._bias_grad(g, m.conv_in.bias)
         w = m.conv_in.weight
-        if forms.current().train_smallconv and w.shape[1] == 3 and g.C in (32, 64) and self.x.is_contiguous():
-            K.stem_wgrad(self.x, g, self._pgrad(w))  # fp32 VALU, the 3 input channels unpadded
+        if forms.current().train_smallconv and w.shape[1] == 3 and g.C in (32, 64) and x.is_contiguous():
+            K.stem_wgrad(x, g, self._pgrad(w))  # fp32 VALU, the 3 input channels unpadded
             return
-        xn = K.nchw_to_nhwc(self.x, 4)
+        xn = K.nchw_to_nhwc(x, 4)
         self._wgrad(g, [Seg(View.full(xn), TAPS3)], self._pgrad(w), (w.shape[1] * 9, 9, 1), Cw=w.shape[1])
 
-    def _temb_bwd(self):
+    _BWD = {ResRec: _bwd_res, AttnRec: _bwd_attn, DownRec: _bwd_down, UpRec: _bwd_up, ConvInRec: _bwd_conv_in}
+
+    def _temb_bwd(self, tape: Tape):
         """t_proj (Linear, SiLU, Linear) and the t_emb_layers (SiLU, Linear) backward (B x 128)."""
         m = self.model
-        w1, b1, w2, b2 = self.tproj
+        w1, b1, w2, b2 = tape.tproj
         D = w1.shape[0]
         B, P = self.dproj.shape
-        e = K.time_embedding(self.tt, D)
+        e = K.time_embedding(tape.tt, D)
         a1 = b1.expand(B, D).contiguous()
         K.gemm_small(B, D, D, e, (D, 1), w1, (1, D), a1, D, beta=1.0)
         h1 = K.silu_map(a1)
@@ -917,13 +952,11 @@ class TrainEngine:
         K.gemm_small(B, D, D, h1, (D, 1), w2, (1, D), a2, D, beta=1.0)
         s = K.silu_map(a2)
         dp = self.dproj
-        for rp in self.res_rows:
-            off, co = rp['off'], rp['co']
-            lin = rp['temb']
-            K.gemm_small(co, D, B, dp, (1, P), s, (D, 1), self._pgrad(lin.weight), D, offs=(off, 0, 0))
-            K.colsum(dp, self._pgrad(lin.bias), col0=off, ncol=co)
+        for rp in tape.res_rows:
+            K.gemm_small(rp.co, D, B, dp, (1, P), s, (D, 1), self._pgrad(rp.temb.weight), D, offs=(rp.off, 0, 0))
+            K.colsum(dp, self._pgrad(rp.temb.bias), col0=rp.off, ncol=rp.co)
         ds = torch.empty((B, D), dtype=torch.float32, device=self.device)
-        K.gemm_small(B, D, P, dp, (P, 1), self.temb_w, (D, 1), ds, D)
+        K.gemm_small(B, D, P, dp, (P, 1), tape.temb_w, (D, 1), ds, D)
         da2 = K.silu_map(a2, ds)
         tp = m.t_proj
         K.gemm_small(D, D, B, da2, (1, D), h1, (D, 1), self._pgrad(tp[2].weight), D)
