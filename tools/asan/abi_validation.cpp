@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "wc_kernels.h"
+#include "wc_optim.h"
 
 // The library build generates this symbol (the digest of its sources, _build.py); the harness links the
 // objects directly, so it supplies its own for wc_version to refer to.
@@ -79,6 +80,25 @@ int main() {
     std::vector<double> ws(wc_mse_workspace_doubles());
     EXPECT(wc_mse_loss(p, p, 0, nullptr, 1.f, ws.data(), p, nullptr), WC_E_SHAPE);
     EXPECT(wc_mse_loss(p + 1, p, 16, nullptr, 1.f, ws.data(), p, nullptr), WC_E_SHAPE);  // misaligned
+
+    // Optimizer entry points (wc_optim.h): the job table, the clip outputs and the workspace are device
+    // memory the host never reads; null table / outputs / workspace, empty table, no chunks.
+    wc_adam_job jobs[2];
+    std::memset(jobs, 0, sizeof(jobs));
+    EXPECT(wc_adam_step(nullptr, 2, 2, nullptr, 1e-3, 1.0, 0.9, 0.999, 1e-8, 1e-3, 0.0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_adam_step(jobs, 0, 2, nullptr, 1e-3, 1.0, 0.9, 0.999, 1e-8, 1e-3, 0.0, 0, nullptr), WC_E_SHAPE);
+    EXPECT(wc_adam_step(jobs, -1, 2, p, 1e-3, 1.0, 0.9, 0.999, 1e-8, 1e-3, 0.0, 0, nullptr), WC_E_SHAPE);
+    EXPECT(wc_adam_step(jobs, 2, 0, p, 1e-3, 1.0, 0.9, 0.999, 1e-8, 1e-3, 0.01, 1, nullptr), WC_E_SHAPE);
+    EXPECT(wc_grad_norm(nullptr, 2, 2, 1.0, ws.data(), p, p + 1, nullptr), WC_E_ARG);
+    EXPECT(wc_grad_norm(jobs, 2, 2, 1.0, nullptr, p, p + 1, nullptr), WC_E_ARG);
+    EXPECT(wc_grad_norm(jobs, 2, 2, 1.0, ws.data(), nullptr, p + 1, nullptr), WC_E_ARG);
+    EXPECT(wc_grad_norm(jobs, 2, 2, 1.0, ws.data(), p, nullptr, nullptr), WC_E_ARG);
+    EXPECT(wc_grad_norm(jobs, 0, 2, 1.0, ws.data(), p, p + 1, nullptr), WC_E_SHAPE);
+    EXPECT(wc_grad_norm(jobs, 2, -3, 1.0, ws.data(), p, p + 1, nullptr), WC_E_SHAPE);
+    if (wc_optim_chunk_elems() <= 0 || wc_optim_chunk_elems() % 4 != 0 || sizeof(wc_adam_job) % 8 != 0) {
+        std::printf("FAIL wc_optim_chunk_elems / wc_adam_job size\n");
+        ++failures;
+    }
 
     // Round-3 training entry points: weight gradients, split-precision attention backward, bounds.
     wc_wgrad_args wg;

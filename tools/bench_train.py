@@ -1,12 +1,15 @@
 """BASELINE config 3 measurement at 256 px, B=32, per-sample timesteps; prints one JSON line.
 
   python tools/bench_train.py [--mode step|forward] [--batch 32] [--steps 10] [--warmup 2]
+                              [--optimizer torch|wc] [--max-grad-norm X]
 
 mode 'step' (default): the reference's whole training iteration (train_ddpm.py:94-114) —
     opt.zero_grad(); noisy = scheduler.add_noise(images, noise, t); pred = model(noisy, t);
     loss = MSELoss()(pred, noise); loss.backward(); opt.step()
-  with the HIP forward-with-tape and HIP backward (models/train_engine.py) and torch Adam, timed per
-  phase with events.  Arithmetic (the model's conv precision, f16x3 by default): forward convs,
+  with the HIP forward-with-tape and HIP backward (models/train_engine.py) and torch Adam (--optimizer
+  torch, the default, so earlier lines stay comparable) or the HIP optimizer (--optimizer wc:
+  diffusion_model/optim.py, wc_adam_step), timed per phase with events; --max-grad-norm clips by global
+  norm (torch: clip_grad_norm_ before the step; wc: fused into it, wc_grad_norm).  Arithmetic (the model's conv precision, f16x3 by default): forward convs,
   projections and attention f16x3 under static range bounds (GroupNorm, in-projection row norms),
   data-gradient convs f16x3 under per-image absmax bounds of the gradient, weight gradients and the
   attention backward bf16x6 (fp32 MFMA at head dim 192); all fp32-class and checked against float64
@@ -40,6 +43,9 @@ def main():
     ap.add_argument('--cpu-batch', type=int, default=1, help='CPU baseline batch (a bounded sample of B)')
     ap.add_argument('--precision', default='fp32-class', choices=['fp32-class', 'f16', 'bf16'],
                     help="'bf16' / 'f16': the 16-bit training lines (Unet.set_train_precision, single-piece builds)")
+    ap.add_argument('--optimizer', default='torch', choices=['torch', 'wc'],
+                    help="'torch': torch.optim.Adam; 'wc': diffusion_model.optim.Adam (one HIP launch per group)")
+    ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the gradients by global L2 norm')
     args = ap.parse_args()
     if args.mode == 'step':
         return train_step(args)
@@ -112,7 +118,12 @@ def train_step(args):
     if args.precision in ('f16', 'bf16'):
         net.set_train_precision(args.precision)
     net = net.to(dev).train()
-    opt = torch.optim.Adam(net.parameters(), lr=1e-4)  # train_ddpm.py:176 (lr from config.yaml)
+    if args.optimizer == 'wc':
+        from weatherconverter_amd.diffusion_model.optim import Adam
+        opt = Adam(net.parameters(), lr=1e-4, max_grad_norm=args.max_grad_norm)
+    else:
+        opt = torch.optim.Adam(net.parameters(), lr=1e-4)  # train_ddpm.py:176 (lr from config.yaml)
+    params = list(net.parameters())
     crit = torch.nn.MSELoss()
     sched = LinearNoiseScheduler(1000, 0.0001, 0.02)
     B, S = args.batch, args.size
@@ -132,7 +143,11 @@ def train_step(args):
         loss.backward()
         if ev:
             ev[1].record()
+        if args.max_grad_norm is not None and args.optimizer == 'torch':
+            torch.nn.utils.clip_grad_norm_(params, args.max_grad_norm)  # train_ddpm.py:112
         opt.step()
+        if ev:
+            ev[2].record()
         return loss.detach()
 
     for i in range(args.warmup):
@@ -141,15 +156,18 @@ def train_step(args):
     losses, evs = [], []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        e[2].record()
-        losses.append(step(i, (e[0], e[1])))
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[3].record()
+        losses.append(step(i, e))
         evs.append(e)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     ms = el / args.steps * 1e3
-    fwd = sum(e[2].elapsed_time(e[0]) for e in evs) / len(evs)
+    fwd = sum(e[3].elapsed_time(e[0]) for e in evs) / len(evs)
     bwd = sum(e[0].elapsed_time(e[1]) for e in evs) / len(evs)
+    # the optimizer step (with its clipping) on the GPU: events around it, the host enqueues ahead
+    opt_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / len(evs)
+    n_elem = sum(p.numel() for p in params)
     roof = None if args.no_roofline else roofline_leg(kernels, step, args.precision, ms)
     cpu = None if args.no_cpu_baseline else cpu_baseline_leg(args)
     prof = None
@@ -172,12 +190,20 @@ def train_step(args):
         'metric': 'train_ddpm config 3: training iterations/s (add_noise + UNet fwd + MSE + backward + Adam)',
         'value': round(args.steps / el, 4), 'unit': 'iter/s', 'ms_per_iter': round(ms, 2),
         'ms_forward': round(fwd, 2), 'ms_backward': round(bwd, 2), 'ms_adam_and_host': round(ms - fwd - bwd, 2),
+        'ms_optimizer_step_gpu': round(opt_ms, 4),
+        'optimizer_step': {'tensors': len(params), 'elements': n_elem,
+                           'tb_per_s_at_28B_per_element': round(28 * n_elem / (opt_ms * 1e-3) / 1e12, 3),
+                           'source': 'HIP events around opt.step() (and clip_grad_norm_ when clipping with torch), '
+                                     'mean over the timed iterations'},
         'images_per_s': round(B * args.steps / el, 2), 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
         'higher_is_better': True,
         'dtype': DTYPES[args.precision],
         'data': 'synthetic (keyed random-init weights; images U[-1,1], Philox N(0,1) noise, t ~ U[0,1000))',
         'config': {'workload': 'BASELINE config 3 full training iteration', 'global_batch': B, 'image_size': S,
-                   'backward': True, 'optimizer': 'torch.optim.Adam lr 1e-4', 'precision': args.precision},
+                   'backward': True,
+                   'optimizer': 'torch.optim.Adam lr 1e-4' if args.optimizer == 'torch' else
+                                'weatherconverter_amd.diffusion_model.optim.Adam lr 1e-4 (wc_adam_step)',
+                   'optimizer_arg': args.optimizer, 'max_grad_norm': args.max_grad_norm, 'precision': args.precision},
         'train_tflops_algorithmic': round(3 * GFLOP_PER_IMAGE_STEP_256 * B / (ms * 1e-3) / 1e3, 1) if S == 256 else None,
         'loss_finite': bool(torch.isfinite(ls).all()), 'loss_first': float(ls[0]), 'loss_last': float(ls[-1]),
         'roofline': roof,

@@ -27,6 +27,11 @@ NOISE_NONE, NOISE_TENSOR, NOISE_PHILOX = (ABI.constants['WC_NOISE_' + n] for n i
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_PRELU, ACT_TANH01 = (ABI.constants['WC_ACT_' + n] for n in (
     'NONE', 'GELU', 'SILU', 'PRELU', 'TANH01'))
 
+# The optimizer entry points (wc_adam_step, wc_grad_norm) are declared in a header of their own.
+OPTIM_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_optim.h')).read())
+AdamJob = OPTIM_ABI.structs['wc_adam_job']
+_SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions}
+
 _libs = {}
 _active = threading.local()
 
@@ -62,7 +67,7 @@ def active_variant() -> str:
 def _bind(lib, name: str):
     """Give lib.<name> the argument and return types the header declares for it."""
     fn = getattr(lib, name)
-    fn.restype, fn.argtypes = ABI.functions[name]
+    fn.restype, fn.argtypes = _SIGNATURES[name]
     return fn
 
 
@@ -83,7 +88,7 @@ def load(build_if_missing: bool = True):
     verify_source_hash(lib, v)
     forms.announce()  # a run with non-default kernel forms says so before its first native call
     stale_ok = os.environ.get('WC_ALLOW_STALE_LIB', '0') == '1'
-    for name in ABI.functions:
+    for name in _SIGNATURES:
         if stale_ok and not hasattr(lib, name):  # an older A/B build may lack newer entry points
             continue
         _bind(lib, name)

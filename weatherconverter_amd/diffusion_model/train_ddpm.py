@@ -5,14 +5,17 @@ One training iteration of the reference (``train_ddpm.py:94-114``) is
     noisy_im = scheduler.add_noise(images, noise, t)        # :105
     noise_pred = model(noisy_im, t)                         # :106
     loss = criterion(noise_pred, noise)                     # :108, criterion = nn.MSELoss() (:177)
-followed by ``loss.backward()`` and ``optimizer.step()``.  All of it runs on HIP kernels except the
-Adam update (torch's ``optim.Adam`` on the device): ``wc_add_noise`` (per-sample coefficients), the
-UNet forward with per-sample timesteps recording its tape, ``wc_mse_loss`` (fp64-accumulated,
-deterministic mean, fused with d loss / d noise_pred), and ``loss.backward()`` through
-``UnetTrainFunction`` (models/train_engine.py: data and weight gradients, GroupNorm, attention and
-time-embedding backward kernels).  ``training_loss`` is the forward; ``TrainForward`` is the same
-captured into a HIP graph for the forward-only line.  Checkpoints keep the reference format (``:56-68``):
-``{'model_state_dict', 'optimizer_state_dict', 'epoch'}`` saved as ``f'{epoch}-checkpoint.ckpt'``.
+followed by ``loss.backward()`` and ``optimizer.step()``.  All of it runs on HIP kernels:
+``wc_add_noise`` (per-sample coefficients), the UNet forward with per-sample timesteps recording its
+tape, ``wc_mse_loss`` (fp64-accumulated, deterministic mean, fused with d loss / d noise_pred),
+``loss.backward()`` through ``UnetTrainFunction`` (models/train_engine.py: data and weight gradients,
+GroupNorm, attention and time-embedding backward kernels), and the Adam update with the optimizer
+``make_optimizer`` returns (``optim.Adam``: ``wc_adam_step``, one launch per parameter group, and
+``wc_grad_norm`` for clipping by global norm); the reference's own ``torch.optim.Adam`` over the same
+parameters keeps working and shares its ``state_dict`` format.  ``training_loss`` is the forward;
+``TrainForward`` is the same captured into a HIP graph for the forward-only line.  Checkpoints keep the
+reference format (``:56-68``): ``{'model_state_dict', 'optimizer_state_dict', 'epoch'}`` saved as
+``f'{epoch}-checkpoint.ckpt'``.
 """
 import os
 from typing import Optional, Tuple
@@ -22,6 +25,7 @@ import torch
 from .. import kernels as K
 from .config import Config, load_config  # noqa: F401  (reference :19-22)
 from .models.unet_base import Unet
+from .optim import Adam
 from .scheduler.linear_noise_scheduler import LinearNoiseScheduler
 
 
@@ -77,6 +81,14 @@ class TrainForward:
             self.t.copy_(torch.as_tensor(t).reshape(-1))
         self.graph.replay()
         return self.loss
+
+
+def make_optimizer(model: Unet, training_config, *, max_grad_norm: Optional[float] = None) -> Adam:
+    """``train_ddpm.py:190``, ``optimizer = Adam(model.parameters(), lr=config.training.lr)``, with the HIP
+    optimizer.  ``training_config``: the ``Config`` or its ``training`` section.  ``max_grad_norm``: the
+    clipping the reference carries commented out at ``:112``, fused into the step."""
+    training = getattr(training_config, 'training', training_config)
+    return Adam(model.parameters(), lr=training.lr, max_grad_norm=max_grad_norm)
 
 
 # ----------------------------------------------------------------------------------- checkpoints

@@ -1362,6 +1362,87 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor, grad: bool = False):
     return (loss, g) if grad else loss
 
 
+class AdamJobs(NamedTuple):
+    """A device table of wc_adam_job rows: `words` its host copy, six int64 words per row in ONE flat list
+    (what the caller compares to know the table is still current; one list, not one per row: the
+    table is rebuilt every training step and per-row containers make the cyclic GC run inside the
+    host-bound backward), `chunk0` row i's first chunk for i <= njobs (so chunk0[-1] is the chunk
+    count), `dtab` the device tensor that holds it."""
+    words: List[int]
+    chunk0: List[int]
+    dtab: torch.Tensor
+    device: torch.device
+
+
+def adam_jobs(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+              exp_avg_sqs: Sequence[torch.Tensor]) -> AdamJobs:
+    """The device job table adam_step and grad_norm read (uploaded on the current stream): one
+    wc_adam_job per tensor as int64 words (p, g, m, v, n, chunk0).  Operands: non-empty contiguous fp32
+    tensors on one device, g / m / v shaped as p."""
+    _req(len(params) > 0 and len(params) == len(grads) == len(exp_avgs) == len(exp_avg_sqs),
+         'adam jobs: one gradient, exp_avg and exp_avg_sq per parameter, at least one parameter')
+    chunk = _native.load().wc_optim_chunk_elems()
+    dev = params[0].device
+    words, chunk0, what = [], [0], ('parameter', 'gradient', 'exp_avg', 'exp_avg_sq')
+    for k in range(len(params)):
+        p = params[k]
+        for i, ts in enumerate((params, grads, exp_avgs, exp_avg_sqs)):
+            t = ts[k]
+            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
+                    and t.layout == torch.strided and t.shape == p.shape and t.numel() > 0):
+                _req(False, f'adam {what[i]}: a non-empty contiguous fp32 tensor on {dev} shaped as its parameter '
+                            f'(got {t.dtype}, {t.device}, shape {tuple(t.shape)}, strides {t.stride()})')
+            words.append(t.data_ptr())
+        words.append(p.numel())
+        words.append(chunk0[-1])
+        chunk0.append(chunk0[-1] + -(-p.numel() // chunk))
+    _req(chunk0[-1] < 2**31, 'adam jobs: too many chunks for one launch')
+    width = ctypes.sizeof(_native.AdamJob) // 8
+    tab = torch.empty((len(params), width), dtype=torch.int64, pin_memory=True)  # as _job_table, from flat words
+    tab.copy_(torch.tensor(words, dtype=torch.int64).view(-1, width))
+    return AdamJobs(words, chunk0, tab.to(dev, non_blocking=True), dev)
+
+
+def _adam_slice(jobs: AdamJobs, first: int, count: Optional[int]):
+    njobs = len(jobs.chunk0) - 1
+    count = njobs - first if count is None else count
+    _req(0 <= first and count > 0 and first + count <= njobs, 'adam jobs: row range outside the table')
+    table = ctypes.cast(jobs.dtab.data_ptr() + first * ctypes.sizeof(_native.AdamJob), ctypes.POINTER(_native.AdamJob))
+    return table, count, jobs.chunk0[first + count] - jobs.chunk0[first]
+
+
+def adam_step(jobs: AdamJobs, *, step: int, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float = 0.0,
+              decoupled_weight_decay: bool = False, clip: Optional[torch.Tensor] = None, first: int = 0,
+              count: Optional[int] = None):
+    """torch.optim.Adam's / AdamW's update, at step count `step` >= 1, of the table's rows
+    [first, first + count) in ONE launch (wc_adam_step), in place: p, exp_avg and exp_avg_sq are written
+    through their addresses (the caller bumps the parameters' version counters).  clip: an fp32 device
+    scalar every gradient is multiplied by as it is read (grad_norm's), or None."""
+    _req(step >= 1, 'adam_step: step count >= 1')
+    if clip is not None:
+        _req(clip.is_cuda and clip.device == jobs.device and clip.dtype == torch.float32 and clip.numel() == 1,
+             'adam_step clip: one fp32 value on the parameters\' device')
+    table, n, nchunks = _adam_slice(jobs, first, count)
+    step_size = lr / (1.0 - beta1**step)
+    bc2_sqrt = (1.0 - beta2**step)**0.5
+    with torch.cuda.device(jobs.device):
+        _native.call('wc_adam_step', table, n, nchunks, _ptr(clip), step_size, bc2_sqrt, beta1, beta2, eps, lr,
+                     weight_decay, int(decoupled_weight_decay), _stream())
+
+
+def grad_norm(jobs: AdamJobs, max_norm: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(norm, clip), 0-dim fp32 device tensors: the L2 norm of all the table's gradients together and
+    min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s total_norm and coefficient
+    (wc_grad_norm: fp64 sums in a fixed order, no host synchronisation; the gradients are only read)."""
+    table, n, nchunks = _adam_slice(jobs, 0, None)
+    with torch.cuda.device(jobs.device):
+        ws = torch.empty(nchunks, dtype=torch.float64, device=jobs.device)
+        out = torch.empty(2, dtype=torch.float32, device=jobs.device)
+        _native.call('wc_grad_norm', table, n, nchunks, float(max_norm), ws.data_ptr(), out.data_ptr(),
+                     out.data_ptr() + 4, _stream())
+    return out[0], out[1]
+
+
 def philox_normal(shape, device, seed: int, sample0: int = 0, step: int = 0) -> torch.Tensor:
     out = torch.empty(shape, dtype=torch.float32, device=device)
     B = shape[0]
