@@ -1,7 +1,7 @@
 """BASELINE config 3 measurement at 256 px, B=32, per-sample timesteps; prints one JSON line.
 
   python tools/bench_train.py [--mode step|forward] [--batch 32] [--steps 10] [--warmup 2]
-                              [--optimizer torch|wc] [--max-grad-norm X]
+                              [--optimizer torch|wc] [--max-grad-norm X] [--ema none|torch|wc]
 
 mode 'step' (default): the reference's whole training iteration (train_ddpm.py:94-114) —
     opt.zero_grad(); noisy = scheduler.add_noise(images, noise, t); pred = model(noisy, t);
@@ -9,7 +9,10 @@ mode 'step' (default): the reference's whole training iteration (train_ddpm.py:9
   with the HIP forward-with-tape and HIP backward (models/train_engine.py) and torch Adam (--optimizer
   torch, the default, so earlier lines stay comparable) or the HIP optimizer (--optimizer wc:
   diffusion_model/optim.py, wc_adam_step), timed per phase with events; --max-grad-norm clips by global
-  norm (torch: clip_grad_norm_ before the step; wc: fused into it, wc_grad_norm).  Arithmetic (the model's conv precision, f16x3 by default): forward convs,
+  norm (torch: clip_grad_norm_ before the step; wc: fused into it, wc_grad_norm).  --ema adds the
+  exponential moving average of the weights after the step (decay 0.9999), timed with events of its own
+  (ms_ema_update_gpu): 'torch' is torch._foreach_lerp_ over the parameters, 'wc' is diffusion_model/ema.py
+  (wc_ema_update, one launch over the same tensors).  Arithmetic (the model's conv precision, f16x3 by default): forward convs,
   projections and attention f16x3 under static range bounds (GroupNorm, in-projection row norms),
   data-gradient convs f16x3 under per-image absmax bounds of the gradient, weight gradients and the
   attention backward bf16x6 (fp32 MFMA at head dim 192); all fp32-class and checked against float64
@@ -46,6 +49,8 @@ def main():
     ap.add_argument('--optimizer', default='torch', choices=['torch', 'wc'],
                     help="'torch': torch.optim.Adam; 'wc': diffusion_model.optim.Adam (one HIP launch per group)")
     ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the gradients by global L2 norm')
+    ap.add_argument('--ema', default='none', choices=['none', 'torch', 'wc'],
+                    help="average the weights after the step: 'torch' torch._foreach_lerp_, 'wc' diffusion_model.ema.EMA")
     args = ap.parse_args()
     if args.mode == 'step':
         return train_step(args)
@@ -124,6 +129,12 @@ def train_step(args):
     else:
         opt = torch.optim.Adam(net.parameters(), lr=1e-4)  # train_ddpm.py:176 (lr from config.yaml)
     params = list(net.parameters())
+    ema_decay = 0.9999
+    if args.ema == 'wc':
+        from weatherconverter_amd.diffusion_model.ema import EMA
+        ema = EMA(net, ema_decay)
+    elif args.ema == 'torch':
+        shadows = [p.detach().clone() for p in params]
     crit = torch.nn.MSELoss()
     sched = LinearNoiseScheduler(1000, 0.0001, 0.02)
     B, S = args.batch, args.size
@@ -148,6 +159,13 @@ def train_step(args):
         opt.step()
         if ev:
             ev[2].record()
+        if args.ema == 'wc':
+            ema.update()
+        elif args.ema == 'torch':
+            with torch.no_grad():
+                torch._foreach_lerp_(shadows, params, 1.0 - ema_decay)
+        if ev:
+            ev[4].record()
         return loss.detach()
 
     for i in range(args.warmup):
@@ -156,7 +174,7 @@ def train_step(args):
     losses, evs = [], []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         e[3].record()
         losses.append(step(i, e))
         evs.append(e)
@@ -167,6 +185,7 @@ def train_step(args):
     bwd = sum(e[0].elapsed_time(e[1]) for e in evs) / len(evs)
     # the optimizer step (with its clipping) on the GPU: events around it, the host enqueues ahead
     opt_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / len(evs)
+    ema_ms = None if args.ema == 'none' else sum(e[2].elapsed_time(e[4]) for e in evs) / len(evs)
     n_elem = sum(p.numel() for p in params)
     roof = None if args.no_roofline else roofline_leg(kernels, step, args.precision, ms)
     cpu = None if args.no_cpu_baseline else cpu_baseline_leg(args)
@@ -195,6 +214,11 @@ def train_step(args):
                            'tb_per_s_at_28B_per_element': round(28 * n_elem / (opt_ms * 1e-3) / 1e12, 3),
                            'source': 'HIP events around opt.step() (and clip_grad_norm_ when clipping with torch), '
                                      'mean over the timed iterations'},
+        'ms_ema_update_gpu': None if ema_ms is None else round(ema_ms, 4),
+        'ema_update': None if ema_ms is None else {
+            'decay': ema_decay, 'tensors': len(params), 'elements': n_elem,
+            'tb_per_s_at_12B_per_element': round(12 * n_elem / (ema_ms * 1e-3) / 1e12, 3),
+            'source': 'HIP events around the EMA update after opt.step(), mean over the timed iterations'},
         'images_per_s': round(B * args.steps / el, 2), 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
         'higher_is_better': True,
         'dtype': DTYPES[args.precision],
@@ -203,7 +227,10 @@ def train_step(args):
                    'backward': True,
                    'optimizer': 'torch.optim.Adam lr 1e-4' if args.optimizer == 'torch' else
                                 'weatherconverter_amd.diffusion_model.optim.Adam lr 1e-4 (wc_adam_step)',
-                   'optimizer_arg': args.optimizer, 'max_grad_norm': args.max_grad_norm, 'precision': args.precision},
+                   'optimizer_arg': args.optimizer, 'max_grad_norm': args.max_grad_norm, 'precision': args.precision,
+                   'ema': {'none': None, 'torch': 'torch._foreach_lerp_ decay 0.9999',
+                           'wc': 'weatherconverter_amd.diffusion_model.ema.EMA decay 0.9999 (wc_ema_update)'}[args.ema],
+                   'ema_arg': args.ema},
         'train_tflops_algorithmic': round(3 * GFLOP_PER_IMAGE_STEP_256 * B / (ms * 1e-3) / 1e3, 1) if S == 256 else None,
         'loss_finite': bool(torch.isfinite(ls).all()), 'loss_first': float(ls[0]), 'loss_last': float(ls[-1]),
         'roofline': roof,

@@ -30,7 +30,10 @@ ACT_NONE, ACT_GELU, ACT_SILU, ACT_PRELU, ACT_TANH01 = (ABI.constants['WC_ACT_' +
 # The optimizer entry points (wc_adam_step, wc_grad_norm) are declared in a header of their own.
 OPTIM_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_optim.h')).read())
 AdamJob = OPTIM_ABI.structs['wc_adam_job']
-_SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions}
+# So are the weight-averaging ones (wc_ema_update, wc_ema_swap).
+EMA_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_ema.h')).read())
+EmaJob = EMA_ABI.structs['wc_ema_job']
+_SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions, **EMA_ABI.functions}
 
 _libs = {}
 _active = threading.local()

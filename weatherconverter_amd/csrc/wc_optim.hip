@@ -14,21 +14,12 @@
 // coalesced one-float-per-lane path.  Nothing outside [0, n) of a tensor is read or written.
 // Elementwise, so deterministic; HBM-bound at 16 B read + 12 B written per element.  The square
 // root and the division are the correctly rounded ones (no fast-math flag on this file).
-#include "wc_common.hpp"
+#include "wc_jobs.hpp"
 #include "wc_optim.h"
 
 namespace {
 
-constexpr int OPT_THREADS = 256;
-constexpr int OPT_VEC = 4;                                 // f32x4 per thread and operand in a full chunk
-constexpr int OPT_CHUNK = OPT_THREADS * OPT_VEC * 4;       // 4096 elements == wc_optim_chunk_elems()
-
-// The tensors' addresses come out of the job table, so the compiler knows no address space for them and
-// would issue flat loads and stores; they are device global memory, and these types say so.
-typedef __attribute__((address_space(1))) float gf32;
-typedef __attribute__((address_space(1))) const float gcf32;
-typedef __attribute__((address_space(1))) f32x4 gf32x4;
-typedef __attribute__((address_space(1))) const f32x4 gcf32x4;
+using namespace wcjobs;  // the chunk geometry, the global pointer types and find_job (shared with wc_ema.hip)
 
 struct AdamHyper {
     float step_size;   // lr / (1 - beta1^step)
@@ -40,16 +31,6 @@ struct AdamHyper {
     float shrink;      // 1 - lr * weight_decay (mode 2)
     int mode;          // 0 no decay, 1 L2, 2 decoupled
 };
-
-// The last job of the table slice whose first chunk is <= c (the slice's first job has chunk0 <= c).
-WC_DEVICE int find_job(const wc_adam_job* __restrict__ jobs, int njobs, int64_t c) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].chunk0 <= c) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // torch/optim/adam.py _single_tensor_adam, fp32.  Every rounding is written out (no contraction left to
 // the compiler), so the vector, tail and one-float paths give the same bits for the same element: the

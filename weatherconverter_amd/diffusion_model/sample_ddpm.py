@@ -5,6 +5,7 @@ with the reference's argument meaning.  Differences, all opt-in or fail-loud:
   * ``sample`` returns the final x0 tensor in addition to writing the PNG grid (``save_path=None``
     skips the file), and takes build-only keywords: ``noise`` ('torch_cpu' = reference RNG stream,
     'philox' = on-device counter-based noise), ``seed``, ``x_T``, ``graph``.
+  * ``load_model`` takes ``weights='ema'``: the averaged weights of a checkpoint saved with an ``EMA``.
   * ``infer`` does not swallow exceptions (reference ``:84-87`` prints and continues).
 Hot loop (reference ``:35-44``) per step: one UNet forward on the HIP engine + one fused scheduler
 kernel.  ``graph=True`` captures the UNet forward + step into a HIP graph once and replays it.
@@ -228,12 +229,21 @@ def sample(model, scheduler: LinearNoiseScheduler, train_config: TrainingConfig,
     return xt
 
 
-def load_model(model_path: str, model_config: ModelConfig) -> torch.nn.Module:
-    """Reference :56-61 — Unet + ``torch.load(...)['model_state_dict']`` (weights_only load)."""
+def load_model(model_path: str, model_config: ModelConfig, *, weights: str = 'model') -> torch.nn.Module:
+    """Reference :56-61 — Unet + ``torch.load(...)['model_state_dict']`` (weights_only load).
+    ``weights='ema'``: the exponential moving average a checkpoint saved with ``ema=`` carries
+    (``ema_state_dict['shadow']``) instead of the raw weights; a file without one raises ``RuntimeError``."""
+    if weights not in ('model', 'ema'):
+        raise ValueError(f"weights must be 'model' or 'ema', got {weights!r}")
     dev = _device()
     model = Unet(model_config).to(dev)
     checkpoint = torch.load(model_path, map_location=dev, weights_only=True)
-    model.load_state_dict(checkpoint['model_state_dict'])
+    if weights == 'ema':
+        if 'ema_state_dict' not in checkpoint:
+            raise RuntimeError(f"load_model: {model_path} has no 'ema_state_dict' (saved without ema=)")
+        model.load_state_dict(checkpoint['ema_state_dict']['shadow'])
+    else:
+        model.load_state_dict(checkpoint['model_state_dict'])
     model.eval()
     return model
 

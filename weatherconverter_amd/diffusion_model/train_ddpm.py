@@ -5,17 +5,20 @@ One training iteration of the reference (``train_ddpm.py:94-114``) is
     noisy_im = scheduler.add_noise(images, noise, t)        # :105
     noise_pred = model(noisy_im, t)                         # :106
     loss = criterion(noise_pred, noise)                     # :108, criterion = nn.MSELoss() (:177)
-followed by ``loss.backward()`` and ``optimizer.step()``.  All of it runs on HIP kernels:
+followed by ``loss.backward()``, ``optimizer.step()`` and, beyond the reference, ``ema.update()`` (the
+exponential moving average of the weights DDPM samples from; ``make_ema``).  All of it runs on HIP kernels:
 ``wc_add_noise`` (per-sample coefficients), the UNet forward with per-sample timesteps recording its
 tape, ``wc_mse_loss`` (fp64-accumulated, deterministic mean, fused with d loss / d noise_pred),
 ``loss.backward()`` through ``UnetTrainFunction`` (models/train_engine.py: data and weight gradients,
 GroupNorm, attention and time-embedding backward kernels), and the Adam update with the optimizer
 ``make_optimizer`` returns (``optim.Adam``: ``wc_adam_step``, one launch per parameter group, and
 ``wc_grad_norm`` for clipping by global norm); the reference's own ``torch.optim.Adam`` over the same
-parameters keeps working and shares its ``state_dict`` format.  ``training_loss`` is the forward;
+parameters keeps working and shares its ``state_dict`` format; then the average's update (``ema.EMA``:
+``wc_ema_update``, one launch for the whole model).  ``training_loss`` is the forward;
 ``TrainForward`` is the same captured into a HIP graph for the forward-only line.  Checkpoints keep the
 reference format (``:56-68``): ``{'model_state_dict', 'optimizer_state_dict', 'epoch'}`` saved as
-``f'{epoch}-checkpoint.ckpt'``.
+``f'{epoch}-checkpoint.ckpt'``; with an ``EMA`` a fourth key ``'ema_state_dict'`` rides along, which the
+reference's loader does not read.
 """
 import os
 from typing import Optional, Tuple
@@ -24,6 +27,7 @@ import torch
 
 from .. import kernels as K
 from .config import Config, load_config  # noqa: F401  (reference :19-22)
+from .ema import EMA
 from .models.unet_base import Unet
 from .optim import Adam
 from .scheduler.linear_noise_scheduler import LinearNoiseScheduler
@@ -91,26 +95,42 @@ def make_optimizer(model: Unet, training_config, *, max_grad_norm: Optional[floa
     return Adam(model.parameters(), lr=training.lr, max_grad_norm=max_grad_norm)
 
 
+def make_ema(model: Unet, decay: float = 0.9999, *, warmup: bool = False) -> EMA:
+    """The exponential moving average of ``model``'s weights, to ``update()`` after every ``optimizer.step()``
+    and to sample from (``with ema.swapped():``, or a checkpoint's ``load_model(..., weights='ema')``)."""
+    return EMA(model, decay, warmup=warmup)
+
+
 # ----------------------------------------------------------------------------------- checkpoints
 def checkpoint_path(folder: str, run_id, epoch: int) -> str:
     """``train_ddpm.py:57`` naming: <checkpoints>/<run_id>/<epoch>-checkpoint.ckpt."""
     return os.path.join(folder, str(run_id), f'{epoch}-checkpoint.ckpt')
 
 
-def save_checkpoint(epoch: int, model: Unet, opt: torch.optim.Optimizer, folder: str, run_id=0) -> str:
-    """``train_ddpm.py:55-59``: {'model_state_dict', 'optimizer_state_dict', 'epoch'}."""
+def save_checkpoint(epoch: int, model: Unet, opt: torch.optim.Optimizer, folder: str, run_id=0, *,
+                    ema: Optional[EMA] = None) -> str:
+    """``train_ddpm.py:55-59``: {'model_state_dict', 'optimizer_state_dict', 'epoch'}, and with ``ema`` a
+    fourth key 'ema_state_dict' (the reference's loader reads its three and ignores it)."""
     path = checkpoint_path(folder, run_id, epoch)
     os.makedirs(os.path.dirname(path), exist_ok=True)
-    torch.save({'model_state_dict': model.state_dict(), 'optimizer_state_dict': opt.state_dict(), 'epoch': epoch},
-               path)
+    ck = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': opt.state_dict(), 'epoch': epoch}
+    if ema is not None:
+        ck['ema_state_dict'] = ema.state_dict()
+    torch.save(ck, path)
     return path
 
 
-def load_checkpoint(model: Unet, opt: Optional[torch.optim.Optimizer], checkpoint_path: str):
+def load_checkpoint(model: Unet, opt: Optional[torch.optim.Optimizer], checkpoint_path: str, *,
+                    ema: Optional[EMA] = None):
     """``train_ddpm.py:62-68`` -> (model, opt, epoch).  Tensors and plain containers only
-    (``weights_only=True``: nothing in the file is executed)."""
+    (``weights_only=True``: nothing in the file is executed).  With ``ema`` the file's 'ema_state_dict' is
+    loaded into it; a file without one raises ``RuntimeError``."""
     ck = torch.load(checkpoint_path, map_location='cpu', weights_only=True)
+    if ema is not None and 'ema_state_dict' not in ck:
+        raise RuntimeError(f"load_checkpoint: {checkpoint_path} has no 'ema_state_dict' (saved without ema=)")
     model.load_state_dict(ck['model_state_dict'])
     if opt is not None and 'optimizer_state_dict' in ck:
         opt.load_state_dict(ck['optimizer_state_dict'])
+    if ema is not None:
+        ema.load_state_dict(ck['ema_state_dict'])
     return model, opt, ck['epoch']

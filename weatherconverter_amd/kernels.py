@@ -1443,6 +1443,68 @@ def grad_norm(jobs: AdamJobs, max_norm: float) -> Tuple[torch.Tensor, torch.Tens
     return out[0], out[1]
 
 
+class EmaJobs(NamedTuple):
+    """A device table of wc_ema_job rows, laid out as AdamJobs: `words` its host copy, four int64 words
+    per row in one flat list, `chunk0` row i's first chunk for i <= njobs, `dtab` the device tensor."""
+    words: List[int]
+    chunk0: List[int]
+    dtab: torch.Tensor
+    device: torch.device
+
+
+def ema_jobs(shadows: Sequence[torch.Tensor], params: Sequence[torch.Tensor]) -> EmaJobs:
+    """The device job table ema_update and ema_swap read (uploaded on the current stream): one wc_ema_job
+    per tensor as int64 words (ema, p, n, chunk0).  Operands: non-empty contiguous fp32 tensors on one
+    device, each shadow shaped as its parameter and sharing no memory with it."""
+    _req(len(params) > 0 and len(params) == len(shadows), 'ema jobs: one shadow per parameter, at least one parameter')
+    chunk = _native.load().wc_optim_chunk_elems()
+    dev = params[0].device
+    words, chunk0, what = [], [0], ('shadow', 'parameter')
+    for k in range(len(params)):
+        p = params[k]
+        for i, ts in enumerate((shadows, params)):
+            t = ts[k]
+            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
+                    and t.layout == torch.strided and t.shape == p.shape and t.numel() > 0):
+                _req(False, f'ema {what[i]}: a non-empty contiguous fp32 tensor on {dev} shaped as its parameter '
+                            f'(got {t.dtype}, {t.device}, shape {tuple(t.shape)}, strides {t.stride()})')
+            words.append(t.data_ptr())
+        nbytes = 4 * p.numel()
+        _req(words[-2] + nbytes <= words[-1] or words[-1] + nbytes <= words[-2],
+             f'ema jobs: shadow {k} overlaps its parameter')
+        words.append(p.numel())
+        words.append(chunk0[-1])
+        chunk0.append(chunk0[-1] + -(-p.numel() // chunk))
+    _req(chunk0[-1] < 2**31, 'ema jobs: too many chunks for one launch')
+    width = ctypes.sizeof(_native.EmaJob) // 8
+    tab = torch.empty((len(params), width), dtype=torch.int64, pin_memory=True)
+    tab.copy_(torch.tensor(words, dtype=torch.int64).view(-1, width))
+    return EmaJobs(words, chunk0, tab.to(dev, non_blocking=True), dev)
+
+
+def _ema_table(jobs: EmaJobs):
+    table = ctypes.cast(jobs.dtab.data_ptr(), ctypes.POINTER(_native.EmaJob))
+    return table, len(jobs.chunk0) - 1, jobs.chunk0[-1]
+
+
+def ema_update(jobs: EmaJobs, decay: float):
+    """shadow += (1 - decay) (p - shadow) for every row of the table in ONE launch (wc_ema_update), in
+    place; the parameters are only read.  0 <= decay <= 1."""
+    decay = float(decay)
+    _req(0.0 <= decay <= 1.0, f'ema_update: decay in [0, 1] (got {decay})')
+    table, n, nchunks = _ema_table(jobs)
+    with torch.cuda.device(jobs.device):
+        _native.call('wc_ema_update', table, n, nchunks, decay, _stream())
+
+
+def ema_swap(jobs: EmaJobs):
+    """Exchange every shadow with its parameter, bit for bit, in ONE launch (wc_ema_swap): both are
+    written through their addresses (the caller bumps the parameters' version counters)."""
+    table, n, nchunks = _ema_table(jobs)
+    with torch.cuda.device(jobs.device):
+        _native.call('wc_ema_swap', table, n, nchunks, _stream())
+
+
 def philox_normal(shape, device, seed: int, sample0: int = 0, step: int = 0) -> torch.Tensor:
     out = torch.empty(shape, dtype=torch.float32, device=device)
     B = shape[0]
