@@ -34,7 +34,9 @@ init_synthetic_(net, seed=0)
 net = net.cuda().eval()
 x = torch.randn((16, 3, 256, 256), device='cuda')
 t = torch.full((16, ), 500, device='cuda', dtype=torch.long)
-with torch.no_grad():
+# WINO_SHAPES_WIDE=1: inside kernels.wino_vp_wide, so the pre-split convs with N % 256 == 0 take the 8-wave
+# form (the instantiations of the two-group sampling graph)
+with torch.no_grad(), K.wino_vp_wide(os.environ.get('WINO_SHAPES_WIDE', '0') == '1'):
     net(x, t)
     torch.cuda.synchronize()
     rec.clear()

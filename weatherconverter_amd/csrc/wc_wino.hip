@@ -48,12 +48,17 @@
 // Ablation switches for timing experiments only (wrong results; tools/wino_ab.sh): bit 0 no SiLU, 1 no
 // GN/SiLU prologue, 2 no halo transform/split/LDS write in the K loop, 3 no weight loads in the K loop,
 // 4 no barrier in the K loop, 5 no halo loads in the K loop, 6 no A-fragment reads in the K loop, 7 no
-// output stores.
+// output stores, 8 no counted wait for the LDS-DMA pieces before the K loop's barrier (pre-split forms), 9 bits
+// 4 and 8 in the 8-wave pre-split form only (every other form keeps its barriers and waits).
 #ifndef WC_ABL
 #define WC_ABL 0
 #endif
 #ifndef WC_WINO_SCALAR
 #define WC_WINO_SCALAR 0
+#endif
+// Halo ring depth of the 8-wave pre-split form (2: a barrier per chunk, for A/B builds)
+#ifndef WC_WINO_VP8_NH
+#define WC_WINO_VP8_NH 4
 #endif
 
 namespace {
@@ -124,8 +129,11 @@ WC_DEVICE float wino_silu_grad(float y) {  // d/dy [y sigmoid(y)], as wc_backwar
 // planes only -- the low piece is zero there, so the pass writes and the conv copies half the bytes.
 constexpr int VPL = WC_SINGLE16 ? 8 : 16;
 
-template <int TH, int BN, int MB = 2, int NW = 4, bool VP = false>
+// NH: halo (and residual centre) buffers of the K loop's ring, 2 or 4 (4: the 8-wave pre-split form, one
+// barrier per two chunks; see the K loop)
+template <int TH, int BN, int MB = 2, int NW = 4, bool VP = false, int NH = 2>
 struct WTile {
+    static_assert(NH == 2 || (NH == 4 && VP), "a ring of two buffers, or of four in a pre-split form");
     static constexpr int NT = 64 * NW;
     static constexpr int WAVES_N = BN / 32;
     static constexpr int WAVES_M = NW / WAVES_N;
@@ -149,6 +157,7 @@ struct WTile {
     static constexpr int C_PER_T = TH * 16 * 4 / NT;  // centre float4 items per thread
     static constexpr int BSTEP = PBN * 64;       // weight bytes of one K-step: [piece 2][k-half 2][PBN][8]
     static constexpr int STEPS = 12;             // (kernel row, position) per chunk
+    static constexpr int lds(bool res) { return NH * HSTAGE + (res ? NH * CSTAGE : 0); }  // dynamic LDS bytes
 };
 
 // MFMA row r (0..31) -> (row, tile) of a 4-row x 8-tile block: the ds_read_b128 lane group
@@ -164,20 +173,23 @@ WC_DEVICE int wg_tile(int r) { return wg_idx(r) & 7; }
 // Winograd-transformed and split by wino_vsplit_kernel (the same arithmetic, once per input instead of
 // once per output-channel tile): its halo planes are copied into LDS by LDS-DMA, no item VALU.  RES: the
 // fused 1x1 residual segment (raw input, f16x3 under the per-image bound abound).
-template <int TH, int BN, int PRO, bool RES, int MB = 2, int NW = 4>
+template <int TH, int BN, int PRO, bool RES, int MB = 2, int NW = 4, int NH = 2>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MB == 4 ? 1 : 2, MB == 4 ? 1 : 2)))
 void conv3x3_wino_kernel(WDev p) {
     static_assert((PRO == 2 || PRO == 0 || PRO == 3) && !(PRO == 0 && RES),
                   "GN+SiLU (+ residual), pre-split GN+SiLU (+ residual) or one raw segment");
     constexpr bool VP = PRO == 3;
-    using T = WTile<TH, BN, MB, NW, VP>;
+    using T = WTile<TH, BN, MB, NW, VP, NH>;
     constexpr int NT = T::NT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* const cbase = smem + 2 * T::HSTAGE;  // residual centre buffers
+    unsigned char* const cbase = smem + NH * T::HSTAGE;  // residual centre buffers
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = tid >> 6;
+    // 8 waves: the wave index as a scalar.  The compiler cannot see that tid >> 6 is wave-uniform, and this
+    // form's weight tile depends on it (wn / WPT): every weight load's scalar offset went through a
+    // readfirstlane loop of its own, and the partial LDS-DMA round through an exec-mask branch.
+    const int wave = NW == 8 ? __builtin_amdgcn_readfirstlane(tid >> 6) & (NW - 1) : tid >> 6;
     const int wm = wave / T::WAVES_N;
     const int wn = wave % T::WAVES_N;
 
@@ -238,13 +250,15 @@ void conv3x3_wino_kernel(WDev p) {
         }
     }
     const int vchunk = VPL * p.H * (p.W / 2) * 16;  // bytes of one 16-channel chunk's planes
-    auto dma_halo = [&](int c, int hs) {
+    // live = false (NH 4: a chunk past the last): the same copies at an out-of-range offset, zeros and no
+    // traffic (the chunk offset c vchunk is a scalar offset, which the range check does not see)
+    auto dma_halo = [&](int c, int hs, bool live = true) {
         if constexpr (VP) {
             unsigned char* dst = smem + hs * T::HSTAGE + wave * 1024;
 #pragma unroll
             for (int i = 0; i < T::DPW; ++i)
                 if (T::DPIECES % NW == 0 || wave + NW * i < T::DPIECES)  // wave-uniform: the partial last round
-                    wino_lds16(srdv, dst + i * NW * 1024, voff[i], c * vchunk);
+                    wino_lds16(srdv, dst + i * NW * 1024, live ? voff[i] : OOB, live ? c * vchunk : 0);
         }
     };
 
@@ -501,16 +515,33 @@ void conv3x3_wino_kernel(WDev p) {
     // Chunk c uses halo buffer (nck0 - 1 - c) & 1, counted from the end, so the peeled last chunk is one
     // compile-time variant flowing into the epilogue (two variants joining there make the register
     // allocator spill, as in wc_conv6.hip)
-    const int pv0 = (p.nck0 - 1) & 1;
+    //
+    // NH = 4 (the 8-wave pre-split form: one workgroup per CU whatever its LDS): chunk c in halo and centre
+    // buffer (nck0 - 1 - c) & 3, one barrier per two chunks -- after every chunk in an even buffer.  The
+    // planes and the centre of chunk c + 2 go out during chunk c into the buffer chunk c - 2 had:
+    //  * free: one of chunks c - 2 and c - 1 sits in an even buffer, so a barrier lies between any wave's last
+    //    read of chunk c - 2 and this fill;
+    //  * landed: one of chunks c and c + 1 ends in a barrier, and the wait before every barrier covers all the
+    //    wave's copies issued so far (below), so chunk c + 2's planes are whole before any wave reads them;
+    //  * a chunk in an odd buffer flows into the next without a barrier: it reads that chunk's step-0 fragments
+    //    under its own last MFMA step.  A chunk in an even buffer reads them after its barrier, the prologue
+    //    after its own: no chunk reads fragments at its head.
+    // The prologue fills the first two chunks (nck0 == 1: chunk 1 as zeros, never read).
+    const int pv0 = (p.nck0 - 1) & (NH - 1);
+    const int pv1 = (pv0 - 1) & (NH - 1);  // NH 4: chunk 1's buffer
     load_halo(0);
     dma_halo(0, pv0);
+    if constexpr (NH == 4) dma_halo(1, pv1, p.nck0 > 1);
     if constexpr (RI) load_centre(I0, 0, nri > 0);
+    if constexpr (RI && NH == 4) load_centre(I1, 1, nri > 1);
     load_w(0, 0);
     load_w(1, 1);
     write_items(pv0);
     if constexpr (RI) write_centre(I0, pv0);
+    if constexpr (RI && NH == 4) write_centre(I1, pv1);
     if constexpr (VP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA pieces landed
     __syncthreads();
+    if constexpr (NH == 4) read_a(0, pv0, 0, 0);
     // The next chunk's halo item slot j goes out at step load_at(j) (after that step's weight loads:
     // vmcnt drains in issue order, so the weight waits of the following steps wait for it only from
     // three steps later); its prologue (step pro_at(j)) and transform (tiles 0 / 1 at the next two
@@ -543,7 +574,12 @@ void conv3x3_wino_kernel(WDev p) {
     auto chunk = [&](auto P, auto L, int c) {
         constexpr int PV = decltype(P)::value;
         constexpr bool LAST = decltype(L)::value != 0;
-        read_a(0, PV, 0, 0);  // step 0's fragments (the halo buffer was written before the last barrier)
+        constexpr int AH = NH / 2;                                 // the chunk filled during this one: c + AH
+        constexpr int FB = (PV + AH) & (NH - 1);                   // its buffer
+        constexpr int NX = (PV + NH - 1) & (NH - 1);               // chunk c + 1's buffer
+        constexpr bool BAR = NH == 2 || LAST || !(PV & 1);         // a barrier ends this chunk
+        // step 0's fragments (the halo buffer was written before the last barrier; NH 4: read already)
+        if constexpr (NH == 2) read_a(0, PV, 0, 0);
 #pragma unroll
         for (int st = 0; st < T::STEPS; ++st) {
             if (!(WC_ABL & 8) || c == 0) load_w((st + 2) % 3, T::STEPS * c + st + 2);
@@ -552,9 +588,10 @@ void conv3x3_wino_kernel(WDev p) {
                 for (int j = 0; j < T::I_PER_T; ++j)
                     if (!(WC_ABL & 32) && st == load_at(j)) load_slot(j, c + 1);
                 if (st == HALO_AT) {
-                    dma_halo(c + 1, PV ^ 1);
+                    if constexpr (NH == 2) dma_halo(c + 1, FB);
+                    else dma_halo(c + AH, FB, c + AH < p.nck0);
                     load_ss(c + 1);
-                    if constexpr (RI) load_centre(I0, c + 1, c + 1 < nri);
+                    if constexpr (RI) load_centre(I0, c + AH, c + AH < nri);
                 }
             } else if constexpr (RES) {  // the tail's first two centres
                 if (st == HALO_AT) load_centre(I0, nri, ntail > 0);
@@ -565,12 +602,17 @@ void conv3x3_wino_kernel(WDev p) {
             }
             __builtin_amdgcn_sched_barrier(0);
             if (st + 1 < T::STEPS && (!(WC_ABL & 64) || c == 0)) read_a((st + 1) & 1, PV, (st + 1) >> 2, (st + 1) & 3);
+            // no barrier before the next chunk: its step-0 fragments, the set continuing modulo 2 (step 11
+            // computes from set 1)
+            if constexpr (!BAR) {
+                if (st + 1 == T::STEPS) read_a(0, NX, 0, 0);
+            }
             mfma_a(st & 1, st % 3, st & 3);
             if constexpr (!LAST) {
 #pragma unroll
-                for (int j = 0; j < T::I_PER_T; ++j) slot_work(j, st - pro_at(j), PV ^ 1);
+                for (int j = 0; j < T::I_PER_T; ++j) slot_work(j, st - pro_at(j), FB);
                 if constexpr (RI) {
-                    if (st == 9) write_centre(I0, PV ^ 1);
+                    if (st == 9) write_centre(I0, FB);
                 }
             }
         }
@@ -579,18 +621,32 @@ void conv3x3_wino_kernel(WDev p) {
                 if (c < nri) compute_res(wres, PV);
             }
             if constexpr (LAST) {
-                if (ntail > 0) write_centre(I0, 1);  // tail chunk k in centre buffer (k + 1) & 1
+                // tail chunk k in centre buffer TB(k & 1).  NH 4: no barrier separates this chunk from the one
+                // before it, whose centre (buffer 1) a slower wave may still be reading, so the tail takes
+                // buffers 2 and 3: their last readers (chunks nck0 - 3 and nck0 - 4) lie behind a barrier,
+                // and nothing but this thread's own earlier write (chunk nck0 - 2's fill, zeros) lands there
+                if (ntail > 0) write_centre(I0, NH == 2 ? 1 : 2);
             }
         }
         // VP: this wave's LDS-DMA pieces of the next chunk (issued at step HALO_AT, followed by at least
         // 18 weight loads) have landed once at most the last 4 vector-memory ops (the next chunk's first
         // two weight steps) are outstanding: vmcnt counts loads in issue order
-        if constexpr (VP && !LAST) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        if constexpr (!(WC_ABL & 16)) __syncthreads();
+        // NH 4: the same count at the barrier that ends an even-buffer chunk c.  In issue order the wave's
+        // last vector-memory ops are: chunk c + 2's copies (step HALO_AT of chunk c), [its centre, ] 9 x 2
+        // weight loads of steps 3-11 (the last two pairs are chunk c + 1's steps 0 and 1) [and 2 residual
+        // weight loads at step 9]; chunk c + 3's copies (the odd-buffer chunk c + 1 issues them) and everything
+        // older lie before those.  So vmcnt(4) leaves only the 4 newest weight loads in flight and retires the
+        // copies of chunks c + 2 and c + 3 -- the two chunks read before the next barrier.
+        constexpr bool ABL_HERE = !(WC_ABL & 512) || (VP && NW == 8);
+        if constexpr (BAR) {
+            if constexpr (VP && !LAST && !((WC_ABL & 256) && ABL_HERE)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            if constexpr (!((WC_ABL & 16) && ABL_HERE)) __syncthreads();
+            if constexpr (NH == 4 && !LAST) read_a(0, NX, 0, 0);
+        }
     };
     const std::integral_constant<int, 0> NL;
     const std::integral_constant<int, 1> LL;
-    {
+    if constexpr (NH == 2) {
         int c = 0;
         if (pv0) chunk(I1, NL, c++);
         for (; c + 1 < p.nck0 - 1; c += 2) {
@@ -598,18 +654,36 @@ void conv3x3_wino_kernel(WDev p) {
             chunk(I1, NL, c + 1);
         }
         chunk(I0, LL, p.nck0 - 1);
+    } else {
+        // the nck0 - 1 chunks before the last run through buffers pv0, pv0 - 1, ..., 1: the first pv0 of them,
+        // then whole rounds of four
+        const std::integral_constant<int, 2> I2;
+        const std::integral_constant<int, 3> I3;
+        int c = 0;
+        if (pv0 == 3) chunk(I3, NL, c++);
+        if (pv0 >= 2) chunk(I2, NL, c++);
+        if (pv0 >= 1) chunk(I1, NL, c++);
+        for (; c < p.nck0 - 1; c += 4) {
+            chunk(I0, NL, c);
+            chunk(I3, NL, c + 1);
+            chunk(I2, NL, c + 2);
+            chunk(I1, NL, c + 3);
+        }
+        chunk(I0, LL, p.nck0 - 1);
     }
     if constexpr (RES) {
         // tail residual chunk nri + k: weights in set k & 1 (the last 3x3 chunk's prefetch put tail steps 0
         // and 1 in sets 0 and 1; from here the load of step k + 2 is issued after step k's MFMAs), centre
-        // registers k & 1, centre buffer (k + 1) & 1
+        // registers k & 1, centre buffer (k + 1) & 1 (NH 4: 2 + (k & 1); the last chunk wrote tail chunk 0's
+        // centre there before its barrier, and behind that barrier every centre buffer is free)
         auto tstep = [&](auto P, int k) {
             constexpr int PV = decltype(P)::value;
-            compute_res(wreg[PV], PV ^ 1);
+            constexpr int TB = NH == 2 ? PV ^ 1 : 2 + PV;  // this tail chunk's centre buffer
+            compute_res(wreg[PV], TB);
             load_w(PV, S0 + k + 2);
             load_centre(P, nri + k + 2, k + 2 < ntail);
             __builtin_amdgcn_sched_barrier(0);
-            if (k + 1 < ntail) write_centre(std::integral_constant<int, PV ^ 1>{}, PV);
+            if (k + 1 < ntail) write_centre(std::integral_constant<int, PV ^ 1>{}, TB ^ 1);
             __syncthreads();
         };
         int k = 0;
@@ -745,13 +819,14 @@ void conv3x3_wino_kernel(WDev p) {
     }
 }
 
-template <int TH, int BN, int PRO, bool RES, int MB = 2, int NW = 4>
+template <int TH, int BN, int PRO, bool RES, int MB = 2, int NW = 4, int NH = 2>
 int launch_wino(const WDev& d, hipStream_t stream) {
-    using T = WTile<TH, BN, MB, NW, PRO == 3>;  // the layout the kernel itself uses (PRO 3: unpadded planes)
-    constexpr int lds = 2 * T::HSTAGE + (RES ? 2 * T::CSTAGE : 0);
+    using T = WTile<TH, BN, MB, NW, PRO == 3, NH>;  // the layout the kernel itself uses (PRO 3: unpadded planes)
+    constexpr int lds = T::lds(RES);
+    static_assert(lds <= 160 * 1024, "the CU's LDS");
     static bool attr_set = false;  // > 64 KiB of dynamic LDS needs an explicit opt-in
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<TH, BN, PRO, RES, MB, NW>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<TH, BN, PRO, RES, MB, NW, NH>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
@@ -761,8 +836,8 @@ int launch_wino(const WDev& d, hipStream_t stream) {
     p.tiles_y = p.H / TH;
     p.ntiles_n = (p.N + BN - 1) / BN;
     dim3 grid(p.B * p.tiles_y * p.tiles_x * p.ntiles_n);
-    WC_SET_NAME("conv3x3_wino_kernel", {WC_TI(TH), WC_TI(BN), WC_TI(PRO), WC_TB(RES), WC_TI(MB), WC_TI(NW)});
-    hipLaunchKernelGGL((conv3x3_wino_kernel<TH, BN, PRO, RES, MB, NW>), grid, dim3(T::NT), lds, stream, p);
+    WC_SET_NAME("conv3x3_wino_kernel", {WC_TI(TH), WC_TI(BN), WC_TI(PRO), WC_TB(RES), WC_TI(MB), WC_TI(NW), WC_TI(NH)});
+    hipLaunchKernelGGL((conv3x3_wino_kernel<TH, BN, PRO, RES, MB, NW, NH>), grid, dim3(T::NT), lds, stream, p);
     WC_CHECK_LAUNCH();
     return WC_OK;
 }
@@ -1047,7 +1122,8 @@ extern "C" int wc_conv3x3_wino_f16x3_vp8(const wc_conv_args* a, const void* w, i
     if (v_bytes != (int64_t)d.B * d.vimg || d.vimg >= (1L << 31)) return WC_E_SHAPE;
     d.vpre = reinterpret_cast<const unsigned char*>(vpre);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return res ? launch_wino<8, 256, 3, true, 2, 8>(d, s) : launch_wino<8, 256, 3, false, 2, 8>(d, s);
+    return res ? launch_wino<8, 256, 3, true, 2, 8, WC_WINO_VP8_NH>(d, s)
+               : launch_wino<8, 256, 3, false, 2, 8, WC_WINO_VP8_NH>(d, s);
 }
 
 // ---- device re-pack for wc_conv3x3_wino_f16x3 (training: the weights change every step) ----
