@@ -263,6 +263,29 @@ def test_conv3x3_wino_raw_segment_vs_float64(B, H, W, Ci, Co):
 
 
 @pytest.mark.gpu
+def test_conv3x3_wino_channel_slice_input():
+    """The raw segment is channels [4, 36) of a 36-channel tensor: its base is 16 bytes into a pixel and
+    ldc % 4 == 0, so wino_eligible says yes and the launch succeeds (predicate and library agree)."""
+    from weatherconverter_amd import kernels as K
+    B, H, W, Ci, Co = 1, 8, 16, 32, 128
+    g = torch.Generator().manual_seed(53)
+    wide = torch.randn((B, H, W, Ci + 4), generator=g) * 3
+    w = torch.randn((Co, Ci, 3, 3), generator=g) / (Ci * 9)**0.5
+    ref = F.conv2d(_nchw(wide[..., 4:]).double(), w.double(), padding=1)
+    v = K.View(wide.cuda(), 4, Ci)
+    bound = v.tensor().abs().reshape(B, -1).amax(1).contiguous()
+    segs = [K.Seg(v, TAPS3)]
+    assert K.wino_eligible(segs, Co, H, W)
+    wino, direct = torch.empty((B, H, W, Co), device='cuda'), torch.empty((B, H, W, Co), device='cuda')
+    K.conv3x3_wino(segs, K.pack_wino(_pack(w).cuda(), Ci), None, K.View.full(wino), Hm=H, Wm=W, a_exp=60, a_bound=bound)
+    K.conv3x3_f16x3(segs, K.pack_f16x3(_pack(w).cuda(), Ci), None, K.View.full(direct), Hm=H, Wm=W, a_exp=60,
+                    a_bound=bound)
+    torch.cuda.synchronize()
+    ew, ed = rel_l2(_nchw(wino.cpu()).double(), ref), rel_l2(_nchw(direct.cpu()).double(), ref)
+    assert ew < 1e-5 and ew <= 4 * ed + 2e-7, (ew, ed)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('B,H,W,Ci,Co,Cr', [(2, 16, 32, 64, 128, 0), (1, 32, 16, 48, 256, 48), (1, 16, 16, 32, 128, 96),
                                             (2, 32, 32, 128, 128, 128), (2, 16, 16, 64, 256, 0), (1, 8, 16, 32, 512, 512),
                                             (3, 8, 32, 64, 768, 0), (2, 16, 16, 256, 128, 256), (2, 16, 48, 32, 64, 0),

@@ -139,6 +139,36 @@ def test_conv3x3_x6_vs_float64(B, H, W, Ci, Co, Cr, pro, act):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('Co', [128, 64])
+def test_conv3x3_x6_channel_slice_input(Co):
+    """The input is channels [4, 36) of a 36-channel tensor: its base is 16 bytes into a pixel and
+    ldc % 4 == 0, so x6_eligible says yes and the launch succeeds (predicate and library agree)."""
+    from weatherconverter_amd import kernels as K
+    B, H, W, Ci = 1, 16, 16, 32
+    g = torch.Generator().manual_seed(11)
+    wide = torch.randn((B, H, W, Ci + 4), generator=g)
+    w = torch.randn((Co, Ci, 3, 3), generator=g) / (Ci * 9)**0.5
+    b = torch.randn(Co, generator=g) * 0.1
+    ref = F.conv2d(_nchw(wide[..., 4:]).double(), w.double(), b.double(), padding=1)
+    segs = [K.Seg(K.View(wide.cuda(), 4, Ci), TAPS3)]
+    assert K.x6_eligible(segs, Co, H, W)
+    wp = _pack(w).cuda()
+    outs = {}
+    for mode in ('x6', 'fp32'):
+        out = K.View.full(torch.empty((B, H, W, Co), device='cuda'))
+        if mode == 'x6':
+            K.conv3x3_x6(segs, K.pack_x6(wp, Ci, 0), b.cuda(), out, Hm=H, Wm=W)
+        else:
+            K.conv_igemm(segs, wp, b.cuda(), out, Hm=H, Wm=W)
+        torch.cuda.synchronize()
+        outs[mode] = _nchw(out.t.cpu())
+    e6 = rel_l2(outs['x6'].double(), ref)
+    e32 = rel_l2(outs['fp32'].double(), ref)
+    assert e6 < 1e-5
+    assert e6 <= 4 * e32 + 1e-7, (e6, e32)
+
+
+@pytest.mark.gpu
 def test_conv3x3_x6_rejects_untiled_shape():
     from weatherconverter_amd import kernels as K
     h = torch.randn((1, 12, 16, 32), device='cuda')

@@ -12,6 +12,8 @@
 #include "wc_kernels.h"
 #include "wc_optim.h"
 
+#include "conv_args_mutations.hpp"
+
 // The library build generates this symbol (the digest of its sources, _build.py); the harness links the
 // objects directly, so it supplies its own for wc_version to refer to.
 extern "C" const char* wc_source_hash(void) { return "asan-harness"; }
@@ -153,6 +155,9 @@ int main() {
         std::printf("FAIL sizing helpers\n");
         ++failures;
     }
+
+    // The wc_conv_args entry points, one fault at a time.
+    failures += mut::run_all();
 
     std::printf("abi_validation: %d failure(s)\n", failures);
     return failures == 0 ? 0 : 1;

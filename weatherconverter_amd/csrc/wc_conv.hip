@@ -27,6 +27,7 @@
 //   segment 1 (optional)     the 1x1 residual_input_conv appended as extra K columns (raw input)
 //   epilogue                 + bias[n] + temb[b,n] + residual view, NHWC or NCHW store
 #include "wc_common.hpp"
+#include "wc_conv_host.hpp"
 
 namespace {
 
@@ -411,41 +412,20 @@ extern "C" int wc_conv_igemm(const wc_conv_args* a, void* stream) {
     if (a->absmax_out || a->gn_part) return WC_E_ARG;  // output bounds / GN partials: split-precision kernels
     ConvDev d{};
     const wc_conv_seg& s0 = a->seg[0];
-    if (!s0.src) return WC_E_ARG;
-    if (s0.C <= 0 || s0.C % BK != 0 || s0.ldc % 4 != 0) return WC_E_SHAPE;
-    if (s0.ntaps < 1 || s0.ntaps > WC_MAX_TAPS) return WC_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(s0.src) & 15) != 0) return WC_E_SHAPE;
     if ((s0.scale == nullptr) != (s0.shift == nullptr)) return WC_E_ARG;
-    if (s0.kbase != 0) return WC_E_SHAPE;
-    if ((long)a->B * s0.H * s0.W * s0.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;  // 2 GiB SRD range
-    // the taps must form a kh x kw grid: tap t = (ty0 + (t / kw) * tdy, tx0 + (t % kw) * tdx)
-    int kw = 1;
-    while (kw < s0.ntaps && s0.dy[kw] == s0.dy[0]) ++kw;
-    if (s0.ntaps % kw != 0) return WC_E_SHAPE;
-    const int kh = s0.ntaps / kw;
-    const int tdx = kw > 1 ? s0.dx[1] - s0.dx[0] : 0;
-    const int tdy = kh > 1 ? s0.dy[kw] - s0.dy[0] : 0;
-    for (int t = 0; t < s0.ntaps; ++t)
-        if (s0.dy[t] != s0.dy[0] + (t / kw) * tdy || s0.dx[t] != s0.dx[0] + (t % kw) * tdx) return WC_E_SHAPE;
+    if (const int st = wchost::check_src_seg(s0, a->B, BK)) return st;
+    if (s0.kbase != 0 || wchost::taps_any_grid(s0, d.kh, d.kw, d.ty0, d.tdy, d.tx0, d.tdx)) return WC_E_SHAPE;
     d.src0 = s0.src; d.C0 = s0.C; d.ldc0 = s0.ldc; d.H0 = s0.H; d.W0 = s0.W; d.sy = s0.sy; d.sx = s0.sx;
-    d.kh = kh; d.kw = kw; d.ty0 = s0.dy[0]; d.tdy = tdy; d.tx0 = s0.dx[0]; d.tdx = tdx;
     d.scale = s0.scale; d.shift = s0.shift;
     long k = (long)s0.ntaps * s0.C;
     if (a->nseg == 2) {
-        // the fused residual: raw 1x1 read of a view with the same spatial grid as segment 0
         const wc_conv_seg& s1 = a->seg[1];
-        if (!s1.src || s1.scale) return WC_E_ARG;
-        if (s1.C <= 0 || s1.C % BK != 0 || s1.ldc % 4 != 0) return WC_E_SHAPE;
-        if ((reinterpret_cast<uintptr_t>(s1.src) & 15) != 0) return WC_E_SHAPE;
-        if (s1.ntaps != 1 || s1.dy[0] != 0 || s1.dx[0] != 0) return WC_E_SHAPE;
-        if (s1.H != s0.H || s1.W != s0.W || s1.sy != s0.sy || s1.sx != s0.sx) return WC_E_SHAPE;
-        if (s1.kbase != k) return WC_E_SHAPE;
-        if ((long)a->B * s1.H * s1.W * s1.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;
+        if (const int st = wchost::check_res_seg(s1, s0, k, a->B, BK)) return st;
         d.src1 = s1.src; d.C1 = s1.C; d.ldc1 = s1.ldc; d.kbase1 = s1.kbase;
         k += s1.C;
     }
     if (k > a->ldw) return WC_E_SHAPE;
-    if (a->ldw % 4 != 0 || (reinterpret_cast<uintptr_t>(a->w) & 15) != 0) return WC_E_SHAPE;
+    if (a->ldw % 4 != 0 || !wchost::aligned16(a->w)) return WC_E_SHAPE;
     if ((long)a->N * a->ldw * 4 >= (1L << 31)) return WC_E_SHAPE;
     d.B = a->B; d.Hm = a->Hm; d.Wm = a->Wm; d.N = a->N;
     long M = (long)a->B * a->Hm * a->Wm;

@@ -43,6 +43,7 @@
 // + bias[n] + temb[b,n], activation, + residual view, NHWC store.
 #include <stdlib.h>
 
+#include "wc_conv_host.hpp"
 #include "wc_x6.hpp"
 
 namespace {
@@ -898,60 +899,44 @@ int dispatch6(const X6Dev& d, int pro, bool res, bool f3, hipStream_t s) {
     }
 }
 
-bool is_3x3(const wc_conv_seg& s) {
-    if (s.ntaps != 9) return false;
-    for (int t = 0; t < 9; ++t)
-        if (s.dy[t] != t / 3 - 1 || s.dx[t] != t % 3 - 1) return false;
-    return true;
+using namespace wchost;
+
+// What the halo kernel's three maps share, after each entry point's own tap grid and strides: the TH x 16
+// tiling of the main grid (segment 0 spans `in` x it), the source-segment rule, the weights' base; fills d.
+int halo_common(const wc_conv_args* a, const void* w, int in, X6Dev& d, int& BN, int& TH) {
+    const wc_conv_seg& s0 = a->seg[0];
+    BN = wc_conv3x3_x6_tile_n(a->N);
+    TH = BN == 64 ? 16 : 8;
+    if (s0.kbase != 0 || a->B <= 0 || a->N <= 0) return WC_E_SHAPE;
+    if (s0.H != in * a->Hm || s0.W != in * a->Wm || a->Hm % TH || a->Wm % 16) return WC_E_SHAPE;
+    if (const int st = check_src_seg(s0, a->B, 16)) return st;
+    if (!aligned16(w)) return WC_E_SHAPE;
+    d = X6Dev{};
+    d.src0 = s0.src; d.C0 = s0.C; d.ldc0 = s0.ldc; d.nck0 = s0.C / 16;
+    d.B = a->B; d.H = a->Hm; d.W = a->Wm; d.N = a->N;
+    d.w6 = w; d.bias = a->bias; d.res = a->res; d.ldres = a->ldres; d.out = a->out; d.ldo = a->ldo;
+    d.absmax = a->absmax_out;
+    return WC_OK;
 }
 
-// Shared host validation; fills d and returns the number of K-steps (or a negative status).
+// Shared host validation of the 3x3 entry points; fills d.
 int prepare(const wc_conv_args* a, const void* w, X6Dev& d, int& BN, int& TH) {
     if (!a || !w || !a->out) return WC_E_ARG;
     if (a->nseg < 1 || a->nseg > 2) return WC_E_ARG;
     const wc_conv_seg& s0 = a->seg[0];
-    if (!s0.src) return WC_E_ARG;
-    if ((s0.scale == nullptr) != (s0.shift == nullptr)) return WC_E_ARG;
+    if (!s0.src || (s0.scale == nullptr) != (s0.shift == nullptr)) return WC_E_ARG;
     if (a->act < WC_ACT_NONE || a->act > WC_ACT_SILU) return WC_E_ARG;
-    BN = wc_conv3x3_x6_tile_n(a->N);
-    TH = BN == 64 ? 16 : 8;
-    if (!is_3x3(s0) || s0.sy != 1 || s0.sx != 1 || s0.kbase != 0) return WC_E_SHAPE;
-    if (s0.C <= 0 || s0.C % 16 || s0.ldc % 4 || (reinterpret_cast<uintptr_t>(s0.src) & 15)) return WC_E_SHAPE;
-    if (s0.H != a->Hm || s0.W != a->Wm || a->Hm % TH || a->Wm % 16) return WC_E_SHAPE;
-    if (a->B <= 0 || a->N <= 0) return WC_E_SHAPE;
-    if ((long)a->B * s0.H * s0.W * s0.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;  // 2 GiB SRD range
-    if (reinterpret_cast<uintptr_t>(w) & 15) return WC_E_SHAPE;
-    d = X6Dev{};
-    d.src0 = s0.src; d.C0 = s0.C; d.ldc0 = s0.ldc; d.scale = s0.scale; d.shift = s0.shift;
-    d.nck0 = s0.C / 16;
+    if (!taps_grid(s0, 3, 3, -1, -1) || s0.sy != 1 || s0.sx != 1) return WC_E_SHAPE;
+    if (const int st = halo_common(a, w, 1, d, BN, TH)) return st;
+    d.scale = s0.scale; d.shift = s0.shift;
+    d.temb = a->temb; d.temb_ld = a->temb_ld; d.act = a->act;
     if (a->nseg == 2) {
         const wc_conv_seg& s1 = a->seg[1];
-        if (!s1.src || s1.scale) return WC_E_ARG;
-        if (s1.ntaps != 1 || s1.dy[0] != 0 || s1.dx[0] != 0 || s1.sy != 1 || s1.sx != 1) return WC_E_SHAPE;
-        if (s1.H != s0.H || s1.W != s0.W || s1.kbase != 9 * s0.C) return WC_E_SHAPE;
-        if (s1.C <= 0 || s1.C % 16 || s1.ldc % 4 || (reinterpret_cast<uintptr_t>(s1.src) & 15)) return WC_E_SHAPE;
-        if ((long)a->B * s1.H * s1.W * s1.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;
+        if (const int st = check_res_seg(s1, s0, 9 * s0.C, a->B, 16)) return st;
         d.src1 = s1.src; d.C1 = s1.C; d.ldc1 = s1.ldc; d.nck1 = s1.C / 16;
     }
-    if (a->out_nchw || a->Ho != a->Hm || a->Wo != a->Wm || a->osy != 1 || a->osx != 1 || a->ooy || a->oox)
-        return WC_E_SHAPE;
-    // the epilogue addresses one image of the output / residual with 32-bit buffer offsets
-    if ((long)a->Hm * a->Wm * a->ldo * 4 >= (1L << 31) || (a->res && (long)a->Hm * a->Wm * a->ldres * 4 >= (1L << 31)))
-        return WC_E_SHAPE;
-    d.B = a->B; d.H = a->Hm; d.W = a->Wm; d.N = a->N;
-    d.w6 = w; d.bias = a->bias; d.temb = a->temb; d.temb_ld = a->temb_ld;
-    d.res = a->res; d.ldres = a->ldres; d.out = a->out; d.ldo = a->ldo; d.act = a->act;
-    d.a_exp = 0; d.abound = nullptr; d.wsinv = nullptr;
-    d.absmax = a->absmax_out;
-    d.gn_part = a->gn_part;
-    if (a->gn_part) {  // N whole 32-channel blocks at a 32-aligned offset; 64-pixel blocks per image
-        const int sw = a->gn_sw;
-        if ((sw != 4 && sw != 8 && sw != 16 && sw != 32) || a->N % 32 || a->gn_c0 % 32 || a->gn_c0 < 0 ||
-            a->gn_c0 + a->N > a->gn_ncb * 32 || a->gn_p64 != 0 || a->gn_np64 * 64 != a->Hm * a->Wm)
-            return WC_E_SHAPE;
-        d.gn_ncb = a->gn_ncb; d.gn_sw = sw; d.gn_c0 = a->gn_c0; d.gn_np64 = a->gn_np64;
-    }
-    return WC_OK;
+    if (check_out_grid(a, 1, false)) return WC_E_SHAPE;
+    return set_gn_part(d, a, a->Hm * a->Wm, false);
 }
 
 }  // namespace
@@ -961,8 +946,7 @@ extern "C" int wc_conv3x3_x6_tile_n(int N) { return N <= 64 ? 64 : 128; }
 extern "C" int wc_conv3x3_x6(const wc_conv_args* a, const void* w6, int64_t w6_bytes, void* stream) {
     X6Dev d;
     int BN, TH;
-    const int st = prepare(a, w6, d, BN, TH);
-    if (st != WC_OK) return st;
+    if (const int st = prepare(a, w6, d, BN, TH)) return st;
     const long ntn = (a->N + BN - 1) / BN;
     const long steps = 9L * d.nck0 + d.nck1;
     if (w6_bytes != ntn * steps * (long)BN * 96 || w6_bytes >= (1L << 31)) return WC_E_SHAPE;
@@ -976,13 +960,12 @@ extern "C" int wc_conv3x3_f16x3(const wc_conv_args* a, const void* w3, int64_t w
                                 const float* w_inv_scale, const float* a_bound, void* stream) {
     X6Dev d;
     int BN, TH;
-    const int st = prepare(a, w3, d, BN, TH);
-    if (st != WC_OK) return st;
+    if (const int st = prepare(a, w3, d, BN, TH)) return st;
     if (!w_inv_scale) return WC_E_ARG;
     // segment 0 needs a range bound: the GN prologue's static one, or (a raw single segment, e.g. a
     // data gradient in the training backward) the per-image bound a_bound
     if (!a->seg[0].scale && (!a_bound || a->nseg != 1)) return WC_E_ARG;
-    if (a_exp < -60 || a_exp > 60) return WC_E_ARG;
+    if (!wchost::exp_ok(a_exp)) return WC_E_ARG;
     const long ntn = (a->N + BN - 1) / BN;
     const long res_step = a_bound ? 64 : 96;  // segment 1 in fp16 (2 pieces) when bounded, else bf16x6
     if (w3_bytes != ntn * (9L * d.nck0 * BN * 64 + (long)d.nck1 * BN * res_step) || w3_bytes >= (1L << 31))
@@ -1012,37 +995,17 @@ extern "C" int wc_conv4x4s2_f16x3(const wc_conv_args* a, const void* w3, int64_t
     if (a->nseg != 1 || a->act != WC_ACT_NONE) return WC_E_ARG;
     const wc_conv_seg& s0 = a->seg[0];
     if (!s0.src || s0.scale || s0.shift) return WC_E_ARG;
-    if (s0.ntaps != 16 || s0.sy != 2 || s0.sx != 2 || s0.kbase != 0) return WC_E_SHAPE;
-    for (int t = 0; t < 16; ++t)
-        if (s0.dy[t] != t / 4 - 1 || s0.dx[t] != t % 4 - 1) return WC_E_SHAPE;
-    const int BN = wc_conv3x3_x6_tile_n(a->N);
+    if (!taps_grid(s0, 4, 4, -1, -1) || s0.sy != 2 || s0.sx != 2) return WC_E_SHAPE;
+    X6Dev d;
+    int BN, TH;
+    if (const int st = halo_common(a, w3, 2, d, BN, TH)) return st;
     if (BN != 128) return WC_E_SHAPE;  // the TH = 8 x BN = 128 form only (N > 64)
-    if (s0.C <= 0 || s0.C % 16 || s0.ldc % 4 || (reinterpret_cast<uintptr_t>(s0.src) & 15)) return WC_E_SHAPE;
-    if (a->B <= 0 || a->Hm % 8 || a->Wm % 16 || s0.H != 2 * a->Hm || s0.W != 2 * a->Wm) return WC_E_SHAPE;
-    if ((long)a->B * s0.H * s0.W * s0.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(w3) & 15) return WC_E_SHAPE;
-    if (a->out_nchw || a->Ho != a->Hm || a->Wo != a->Wm || a->osy != 1 || a->osx != 1 || a->ooy || a->oox)
-        return WC_E_SHAPE;
-    if ((long)a->Hm * a->Wm * a->ldo * 4 >= (1L << 31)) return WC_E_SHAPE;  // per image: offsets from its base
-    if (a->res && ((long)a->Hm * a->Wm * a->ldres * 4 >= (1L << 31) || a->ldres % 4)) return WC_E_SHAPE;
-    X6Dev d{};
-    d.res = a->res; d.ldres = a->ldres;  // epilogue: out = conv + res (the training data gradient accumulates)
-    d.src0 = s0.src; d.C0 = 4 * s0.C; d.ldc0 = s0.ldc;
-    d.nck0 = 4 * s0.C / 16;
+    // epilogue: out = conv + res (the training data gradient accumulates)
+    if (check_out_grid(a, 1, true) || set_gn_part(d, a, a->Hm * a->Wm, false)) return WC_E_SHAPE;
+    d.C0 = 4 * s0.C; d.nck0 = 4 * s0.C / 16;
     d.s2d_cpp = s0.C / 16; d.Hi = s0.H; d.Wi = s0.W;
-    d.B = a->B; d.H = a->Hm; d.W = a->Wm; d.N = a->N;
-    d.w6 = w3; d.bias = a->bias; d.temb = a->temb; d.temb_ld = a->temb_ld;
-    d.out = a->out; d.ldo = a->ldo; d.act = WC_ACT_NONE;
+    d.temb = a->temb; d.temb_ld = a->temb_ld;
     d.a_exp = 60; d.abound = a_bound; d.wsinv = w_inv_scale;
-    d.absmax = a->absmax_out;
-    d.gn_part = a->gn_part;
-    if (a->gn_part) {
-        const int sw = a->gn_sw;
-        if ((sw != 4 && sw != 8 && sw != 16 && sw != 32) || a->N % 32 || a->gn_c0 % 32 || a->gn_c0 < 0 ||
-            a->gn_c0 + a->N > a->gn_ncb * 32 || a->gn_p64 != 0 || a->gn_np64 * 64 != a->Hm * a->Wm)
-            return WC_E_SHAPE;
-        d.gn_ncb = a->gn_ncb; d.gn_sw = sw; d.gn_c0 = a->gn_c0; d.gn_np64 = a->gn_np64;
-    }
     const long ntn = (a->N + BN - 1) / BN;
     if (w3_bytes != ntn * 4L * d.nck0 * BN * 64 || w3_bytes >= (1L << 31)) return WC_E_SHAPE;
     return launch6<8, 128, 0, false, true, false, false, 1, true>(d, reinterpret_cast<hipStream_t>(stream));
@@ -1058,34 +1021,14 @@ extern "C" int wc_convtr4x4s2_f16x3(const wc_conv_args* a, const void* w3, int64
     if (a->nseg != 1 || a->act != WC_ACT_NONE) return WC_E_ARG;
     const wc_conv_seg& s0 = a->seg[0];
     if (!s0.src || s0.scale || s0.shift) return WC_E_ARG;
-    if (s0.sy != 1 || s0.sx != 1 || s0.kbase != 0) return WC_E_SHAPE;
-    const int BN = wc_conv3x3_x6_tile_n(a->N);
-    const int TH = BN == 64 ? 16 : 8;
-    if (s0.C <= 0 || s0.C % 16 || s0.ldc % 4 || (reinterpret_cast<uintptr_t>(s0.src) & 15)) return WC_E_SHAPE;
-    if (a->B <= 0 || a->N <= 0 || s0.H != a->Hm || s0.W != a->Wm || a->Hm % TH || a->Wm % 16) return WC_E_SHAPE;
-    if ((long)a->B * s0.H * s0.W * s0.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(w3) & 15) return WC_E_SHAPE;
-    if (a->out_nchw || a->Ho != 2 * a->Hm || a->Wo != 2 * a->Wm || a->osy != 2 || a->osx != 2 || a->ooy || a->oox ||
-        a->temb)
-        return WC_E_SHAPE;
-    if (4L * a->Hm * a->Wm * a->ldo * 4 >= (1L << 31)) return WC_E_SHAPE;  // per image: offsets from its base
-    if (a->res && (4L * a->Hm * a->Wm * a->ldres * 4 >= (1L << 31) || a->ldres % 4)) return WC_E_SHAPE;
-    X6Dev d{};
-    d.res = a->res; d.ldres = a->ldres;  // epilogue: out = conv + res, at the parity's output pixel
-    d.src0 = s0.src; d.C0 = s0.C; d.ldc0 = s0.ldc; d.nck0 = s0.C / 16;
-    d.B = a->B; d.H = a->Hm; d.W = a->Wm; d.N = a->N;
-    d.w6 = w3; d.bias = a->bias;
-    d.out = a->out; d.ldo = a->ldo; d.act = WC_ACT_NONE;
+    if (s0.sy != 1 || s0.sx != 1) return WC_E_SHAPE;  // (the 2x2 taps per parity are the kernel's own)
+    X6Dev d;
+    int BN, TH;
+    if (const int st = halo_common(a, w3, 1, d, BN, TH)) return st;
+    // epilogue: out = conv + res, at the parity's output pixel; the parities' pixel blocks: parity p owns
+    // blocks p*HW/64 .. of the 4HW/64
+    if (a->temb || check_out_grid(a, 2, true) || set_gn_part(d, a, 4 * a->Hm * a->Wm, false)) return WC_E_SHAPE;
     d.a_exp = 60; d.abound = a_bound; d.wsinv = w_inv_scale;
-    d.absmax = a->absmax_out;
-    d.gn_part = a->gn_part;
-    if (a->gn_part) {  // the parities' pixel blocks: parity p owns blocks p*HW/64 .. of the 4HW/64
-        const int sw = a->gn_sw;
-        if ((sw != 4 && sw != 8 && sw != 16 && sw != 32) || a->N % 32 || a->gn_c0 % 32 || a->gn_c0 < 0 ||
-            a->gn_c0 + a->N > a->gn_ncb * 32 || a->gn_p64 != 0 || a->gn_np64 * 64 != 4 * a->Hm * a->Wm)
-            return WC_E_SHAPE;
-        d.gn_ncb = a->gn_ncb; d.gn_sw = sw; d.gn_c0 = a->gn_c0; d.gn_np64 = a->gn_np64;
-    }
     const long ntn = (a->N + BN - 1) / BN;
     if (w3_bytes != ntn * 4L * 4L * d.nck0 * BN * 64 || w3_bytes >= (1L << 31)) return WC_E_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -20,6 +20,7 @@
 //     conflict-free with no swizzle.
 #include <type_traits>
 
+#include "wc_conv_host.hpp"
 #include "wc_x6.hpp"
 
 namespace {
@@ -839,44 +840,30 @@ int dispatch(const IgDev& d, int pro, int act, bool f3, hipStream_t s) {
 
 namespace {
 
+using namespace wchost;
+
 // Shared host validation (wc_conv_igemm's contract with C % 16); fills d.
 int prepare(const wc_conv_args* a, const void* w6, IgDev& d, long& k) {
     if (!a || !w6 || !a->out) return WC_E_ARG;
     if (a->nseg < 1 || a->nseg > 2) return WC_E_ARG;
     if (a->act < WC_ACT_NONE || a->act > WC_ACT_SILU) return WC_E_ARG;
     const wc_conv_seg& s0 = a->seg[0];
-    if (!s0.src) return WC_E_ARG;
-    if ((s0.scale == nullptr) != (s0.shift == nullptr)) return WC_E_ARG;
-    if (s0.C <= 0 || s0.C % BK || s0.ldc % 4 || (reinterpret_cast<uintptr_t>(s0.src) & 15)) return WC_E_SHAPE;
-    if (s0.ntaps < 1 || s0.ntaps > WC_MAX_TAPS || s0.kbase != 0) return WC_E_SHAPE;
-    if ((long)a->B * s0.H * s0.W * s0.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;  // 2 GiB SRD range
-    int kw = 1;
-    while (kw < s0.ntaps && s0.dy[kw] == s0.dy[0]) ++kw;
-    if (s0.ntaps % kw != 0) return WC_E_SHAPE;
-    const int kh = s0.ntaps / kw;
-    const int tdx = kw > 1 ? s0.dx[1] - s0.dx[0] : 0;
-    const int tdy = kh > 1 ? s0.dy[kw] - s0.dy[0] : 0;
-    for (int t = 0; t < s0.ntaps; ++t)
-        if (s0.dy[t] != s0.dy[0] + (t / kw) * tdy || s0.dx[t] != s0.dx[0] + (t % kw) * tdx) return WC_E_SHAPE;
+    if (!s0.src || (s0.scale == nullptr) != (s0.shift == nullptr)) return WC_E_ARG;
+    if (const int st = check_src_seg(s0, a->B, BK)) return st;
     d = IgDev{};
+    if (s0.kbase != 0 || taps_any_grid(s0, d.kh, d.kw, d.ty0, d.tdy, d.tx0, d.tdx)) return WC_E_SHAPE;
     d.src0 = s0.src; d.C0 = s0.C; d.ldc0 = s0.ldc; d.H0 = s0.H; d.W0 = s0.W; d.sy = s0.sy; d.sx = s0.sx;
-    d.kh = kh; d.kw = kw; d.ty0 = s0.dy[0]; d.tdy = tdy; d.tx0 = s0.dx[0]; d.tdx = tdx;
     d.scale = s0.scale; d.shift = s0.shift;
     k = (long)s0.ntaps * s0.C;
     if (a->nseg == 2) {
         const wc_conv_seg& s1 = a->seg[1];
-        if (!s1.src || s1.scale) return WC_E_ARG;
-        if (s1.C <= 0 || s1.C % BK || s1.ldc % 4 || (reinterpret_cast<uintptr_t>(s1.src) & 15)) return WC_E_SHAPE;
-        if (s1.ntaps != 1 || s1.dy[0] != 0 || s1.dx[0] != 0) return WC_E_SHAPE;
-        if (s1.H != s0.H || s1.W != s0.W || s1.sy != s0.sy || s1.sx != s0.sx) return WC_E_SHAPE;
-        if (s1.kbase != k) return WC_E_SHAPE;
-        if ((long)a->B * s1.H * s1.W * s1.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;
+        if (const int st = check_res_seg(s1, s0, k, a->B, BK)) return st;
         d.src1 = s1.src; d.C1 = s1.C; d.ldc1 = s1.ldc;
         k += s1.C;
     }
     const long M = (long)a->B * a->Hm * a->Wm;
     if (M <= 0 || M > (1L << 30) || a->N <= 0) return WC_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(w6) & 15) return WC_E_SHAPE;
+    if (!aligned16(w6)) return WC_E_SHAPE;
     d.B = a->B; d.Hm = a->Hm; d.Wm = a->Wm; d.N = a->N; d.M = (int)M;
     d.w6 = w6; d.bias = a->bias; d.temb = a->temb; d.temb_ld = a->temb_ld;
     d.res = a->res; d.ldres = a->ldres; d.out = a->out; d.ldo = a->ldo;
@@ -894,16 +881,8 @@ int prepare(const wc_conv_args* a, const void* w6, IgDev& d, long& k) {
     d.wsinv = nullptr; d.abound = nullptr; d.a_exp = 0;
     d.qkv3 = nullptr; d.qC = d.qD = 0;
     d.absmax = a->absmax_out;
-    d.gn_part = a->gn_part;
-    if (a->gn_part) {  // N whole 32-channel blocks at a 32-aligned offset, NHWC output
-        const int sw = a->gn_sw;
-        if ((sw != 4 && sw != 8 && sw != 16 && sw != 32) || a->N % 32 || a->gn_c0 % 32 || a->gn_c0 < 0 ||
-            a->gn_c0 + a->N > a->gn_ncb * 32 || a->out_nchw || (a->Hm * a->Wm) % 64 || a->gn_p64 < 0 ||
-            a->gn_p64 + a->Hm * a->Wm / 64 > a->gn_np64)
-            return WC_E_SHAPE;
-        d.gn_ncb = a->gn_ncb; d.gn_sw = sw; d.gn_c0 = a->gn_c0; d.gn_p64 = a->gn_p64; d.gn_np64 = a->gn_np64;
-    }
-    return WC_OK;
+    if (a->gn_part) d.gn_p64 = a->gn_p64;
+    return set_gn_part(d, a, a->Hm * a->Wm, true);
 }
 
 }  // namespace
@@ -911,8 +890,7 @@ int prepare(const wc_conv_args* a, const void* w6, IgDev& d, long& k) {
 extern "C" int wc_conv_igemm_x6(const wc_conv_args* a, const void* w6, int64_t w6_bytes, void* stream) {
     IgDev d;
     long k;
-    const int st = prepare(a, w6, d, k);
-    if (st != WC_OK) return st;
+    if (const int st = prepare(a, w6, d, k)) return st;
     const int BN = wc_conv3x3_x6_tile_n(a->N);
     const long ntn = (a->N + BN - 1) / BN;
     if (w6_bytes != ntn * (k / BK) * (long)BN * 96 || w6_bytes >= (1L << 31)) return WC_E_SHAPE;
@@ -931,17 +909,16 @@ extern "C" int wc_conv_igemm_f16x3_qkv(const wc_conv_args* a, const void* w3, in
     if (a->seg[0].ntaps != 1 || a->seg[0].dy[0] || a->seg[0].dx[0] || a->seg[0].sy != 1 || a->seg[0].sx != 1)
         return WC_E_SHAPE;
     if ((a->Hm * a->Wm) % 128 || (reinterpret_cast<uintptr_t>(qkv3) & 15)) return WC_E_SHAPE;
-    if (a_exp < -60 || a_exp > 60) return WC_E_ARG;
+    if (!wchost::exp_ok(a_exp)) return WC_E_ARG;
     for (int i = 0; i < 3; ++i)
-        if (exps[i] < -60 || exps[i] > 60) return WC_E_ARG;
+        if (!wchost::exp_ok(exps[i])) return WC_E_ARG;
     IgDev d;
     long k;
     wc_conv_args aa = *a;
     aa.out = reinterpret_cast<float*>(qkv3);  // unused by the split epilogue; keeps prepare's checks uniform
     aa.ldo = a->N;
     aa.Ho = a->Hm; aa.Wo = a->Wm; aa.osy = aa.osx = 1; aa.ooy = aa.oox = 0;
-    const int st = prepare(&aa, w3, d, k);
-    if (st != WC_OK) return st;
+    if (const int st = prepare(&aa, w3, d, k)) return st;
     const int BN = wc_conv3x3_x6_tile_n(a->N);
     if (BN != 128) return WC_E_SHAPE;
     const long ntn = (a->N + BN - 1) / BN;
@@ -960,9 +937,8 @@ extern "C" int wc_conv_igemm_f16x3(const wc_conv_args* a, const void* w3, int64_
                                    const float* w_inv_scale, const float* a_bound, void* stream) {
     IgDev d;
     long k;
-    const int st = prepare(a, w3, d, k);
-    if (st != WC_OK) return st;
-    if (!w_inv_scale || a_exp < -60 || a_exp > 60) return WC_E_ARG;
+    if (const int st = prepare(a, w3, d, k)) return st;
+    if (!w_inv_scale || !wchost::exp_ok(a_exp)) return WC_E_ARG;
     const int BN = wc_conv3x3_x6_tile_n(a->N);
     const long ntn = (a->N + BN - 1) / BN;
     const long s1 = d.steps - d.steps0;
@@ -1383,8 +1359,7 @@ int prepare_pa(const wc_conv_args* a, const void* a3, int64_t a3_bytes, const vo
     if (s0.ntaps != 1 || s0.dy[0] || s0.dx[0] || s0.sy != 1 || s0.sx != 1 || s0.H != a->Hm || s0.W != a->Wm)
         return WC_E_SHAPE;
     if ((a->Hm * a->Wm) % 128 || s0.C % 32 || a->N % 128) return WC_E_SHAPE;
-    const int st = prepare(a, w3, d, k);
-    if (st != WC_OK) return st;
+    if (const int st = prepare(a, w3, d, k)) return st;
     if (a3_bytes != (long)d.M * s0.C * 4) return WC_E_SHAPE;
     d.a3 = reinterpret_cast<const unsigned char*>(a3);
     return WC_OK;
@@ -1396,7 +1371,7 @@ extern "C" int wc_split_f16x3_tiled(const float* src, int ldc, int B, int HW, in
                                     const float* shift, int silu, int a_exp, void* a3, int64_t a3_bytes,
                                     void* stream) {
     if (!src || !a3 || (scale == nullptr) != (shift == nullptr)) return WC_E_ARG;
-    if (a_exp < -60 || a_exp > 60) return WC_E_ARG;
+    if (!wchost::exp_ok(a_exp)) return WC_E_ARG;
     if (B <= 0 || HW <= 0 || HW % 128 || C <= 0 || C % 32 || ldc < C || ldc % 4) return WC_E_SHAPE;
     if ((reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(a3) & 15)) return WC_E_SHAPE;
     if (scale && ((reinterpret_cast<uintptr_t>(scale) & 15) || (reinterpret_cast<uintptr_t>(shift) & 15)))
@@ -1413,11 +1388,10 @@ extern "C" int wc_split_f16x3_tiled(const float* src, int ldc, int B, int HW, in
 
 extern "C" int wc_proj_f16x3(const wc_conv_args* a, const void* a3, int64_t a3_bytes, const void* w3,
                              int64_t w3_bytes, int a_exp, const float* w_inv_scale, void* stream) {
-    if (!a || !w_inv_scale || a_exp < -60 || a_exp > 60) return WC_E_ARG;
+    if (!a || !w_inv_scale || !wchost::exp_ok(a_exp)) return WC_E_ARG;
     IgDev d;
     long k;
-    const int st = prepare_pa(a, a3, a3_bytes, w3, d, k);
-    if (st != WC_OK) return st;
+    if (const int st = prepare_pa(a, a3, a3_bytes, w3, d, k)) return st;
     if (!d.ident || d.ldo % 4 || (reinterpret_cast<uintptr_t>(d.out) & 15)) return WC_E_SHAPE;
     if (d.res && (d.ldres % 4 || (reinterpret_cast<uintptr_t>(d.res) & 15))) return WC_E_SHAPE;
     if (a->temb) return WC_E_ARG;
@@ -1430,20 +1404,19 @@ extern "C" int wc_proj_f16x3(const wc_conv_args* a, const void* a3, int64_t a3_b
 extern "C" int wc_proj_f16x3_qkv(const wc_conv_args* a, const void* a3, int64_t a3_bytes, const void* w3,
                                  int64_t w3_bytes, int a_exp, const float* w_inv_scale, void* qkv3, int C, int heads,
                                  const int* exps, void* stream) {
-    if (!a || !qkv3 || !exps || !w_inv_scale || a_exp < -60 || a_exp > 60) return WC_E_ARG;
+    if (!a || !qkv3 || !exps || !w_inv_scale || !wchost::exp_ok(a_exp)) return WC_E_ARG;
     if (C <= 0 || heads <= 0 || C % heads || (C / heads) % 32 || a->N != 3 * C) return WC_E_SHAPE;
     if (a->res || a->temb || a->absmax_out || a->gn_part || a->out_nchw) return WC_E_ARG;
     if (reinterpret_cast<uintptr_t>(qkv3) & 15) return WC_E_SHAPE;
     for (int i = 0; i < 3; ++i)
-        if (exps[i] < -60 || exps[i] > 60) return WC_E_ARG;
+        if (!wchost::exp_ok(exps[i])) return WC_E_ARG;
     wc_conv_args aa = *a;
     aa.out = reinterpret_cast<float*>(qkv3);  // unused by the split epilogue; keeps prepare's checks uniform
     aa.ldo = a->N;
     aa.Ho = a->Hm; aa.Wo = a->Wm; aa.osy = aa.osx = 1; aa.ooy = aa.oox = 0;
     IgDev d;
     long k;
-    const int st = prepare_pa(&aa, a3, a3_bytes, w3, d, k);
-    if (st != WC_OK) return st;
+    if (const int st = prepare_pa(&aa, a3, a3_bytes, w3, d, k)) return st;
     if (w3_bytes != (long)(a->N / 128) * d.steps0 * 128 * 64 || w3_bytes >= (1L << 31)) return WC_E_SHAPE;
     d.a_exp = a_exp;
     d.wsinv = w_inv_scale;

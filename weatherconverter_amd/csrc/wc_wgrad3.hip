@@ -27,6 +27,7 @@
 // epilogue removes exactly (power of two).  Results: partial sums per pixel split [split][M][9*C0]
 // (column = tap*C0 + c, the layout of wc_conv_wgrad), reduced in a fixed order by wc_wgrad_reduce:
 // deterministic run to run.
+#include "wc_conv_host.hpp"
 #include "wc_x6.hpp"
 
 namespace {
@@ -359,9 +360,7 @@ static int conv_wgrad3_any(const wc_wgrad_args* a, float* part, int splits, bool
     if (f3 && (!gbound || x_exp < -100 || x_exp > 60)) return WC_E_ARG;
     const wc_conv_seg& s0 = a->seg[0];
     if (!s0.src || (s0.scale == nullptr) != (s0.shift == nullptr)) return WC_E_ARG;
-    if (s0.ntaps != 9 || s0.sy != 1 || s0.sx != 1 || s0.kbase != 0) return WC_E_SHAPE;
-    for (int t = 0; t < 9; ++t)
-        if (s0.dy[t] != t / 3 - 1 || s0.dx[t] != t % 3 - 1) return WC_E_SHAPE;
+    if (!wchost::taps_grid(s0, 3, 3, -1, -1) || s0.sy != 1 || s0.sx != 1 || s0.kbase != 0) return WC_E_SHAPE;
     int WM, TH;
     w3_shape(a->M, WM, TH);
     const int BC = 128 / WM;

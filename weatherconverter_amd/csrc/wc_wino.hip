@@ -43,6 +43,7 @@
 // Reference: unet_base.py:87-109 (ResBlock convs), :146-150 (forward), SURVEY.md §8 row a3.
 #include <stdlib.h>
 
+#include "wc_conv_host.hpp"
 #include "wc_x6.hpp"
 
 // Ablation switches for timing experiments only (wrong results; tools/wino_ab.sh): bit 0 no SiLU, 1 no
@@ -848,6 +849,8 @@ extern "C" int wc_conv3x3_wino_tile_n(int N) { return N <= 64 ? 64 : 128; }
 
 namespace {
 
+using namespace wchost;
+
 // Argument checks and the kernel parameters shared by wc_conv3x3_wino_f16x3 and its pre-split form.
 int wino_setup(const wc_conv_args* a, const void* w, int64_t w_bytes, int a_exp, const float* w_inv_scale,
                const float* a_bound, WDev& d, int& pro, bool& res, int& BN) {
@@ -860,33 +863,24 @@ int wino_setup(const wc_conv_args* a, const void* w, int64_t w_bytes, int a_exp,
     if (pro == 2 && !s0.silu) return WC_E_ARG;
     if (pro == 0 && (!a_bound || a->nseg != 1)) return WC_E_ARG;
     if (a->act != WC_ACT_NONE) return WC_E_ARG;
-    if (a_exp < -60 || a_exp > 60) return WC_E_ARG;
+    if (!wchost::exp_ok(a_exp)) return WC_E_ARG;
     BN = wc_conv3x3_wino_tile_n(a->N);
     const int TH = BN == 64 ? 16 : 8;
-    if (s0.ntaps != 9 || s0.sy != 1 || s0.sx != 1 || s0.kbase != 0) return WC_E_SHAPE;
-    for (int t = 0; t < 9; ++t)
-        if (s0.dy[t] != t / 3 - 1 || s0.dx[t] != t % 3 - 1) return WC_E_SHAPE;
-    if (s0.C <= 0 || s0.C % 16 || s0.ldc % 4 || (reinterpret_cast<uintptr_t>(s0.src) & 15)) return WC_E_SHAPE;
+    if (!taps_grid(s0, 3, 3, -1, -1) || s0.sy != 1 || s0.sx != 1 || s0.kbase != 0) return WC_E_SHAPE;
     if (a->B <= 0 || a->N <= 0 || s0.H != a->Hm || s0.W != a->Wm || a->Hm % TH || a->Wm % 16) return WC_E_SHAPE;
-    if ((long)a->B * s0.H * s0.W * s0.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(w) & 15) return WC_E_SHAPE;
+    if (const int st = check_src_seg(s0, a->B, 16)) return st;
+    if (!aligned16(w)) return WC_E_SHAPE;
     d = WDev{};
     d.src0 = s0.src; d.C0 = s0.C; d.ldc0 = s0.ldc; d.scale = s0.scale; d.shift = s0.shift;
     d.nck0 = s0.C / 16;
     res = a->nseg == 2;
     if (res) {
         const wc_conv_seg& s1 = a->seg[1];
-        if (!s1.src || s1.scale || !a_bound) return WC_E_ARG;  // the residual runs on f16x3 under a_bound
-        if (s1.ntaps != 1 || s1.dy[0] != 0 || s1.dx[0] != 0 || s1.sy != 1 || s1.sx != 1) return WC_E_SHAPE;
-        if (s1.H != s0.H || s1.W != s0.W || s1.kbase != 9 * s0.C) return WC_E_SHAPE;
-        if (s1.C <= 0 || s1.C % 16 || s1.ldc % 4 || (reinterpret_cast<uintptr_t>(s1.src) & 15)) return WC_E_SHAPE;
-        if ((long)a->B * s1.H * s1.W * s1.ldc * 4 >= (1L << 31)) return WC_E_SHAPE;
+        if (!a_bound) return WC_E_ARG;  // the residual runs on f16x3 under a_bound
+        if (const int st = check_res_seg(s1, s0, 9 * s0.C, a->B, 16)) return st;
         d.src1 = s1.src; d.C1 = s1.C; d.ldc1 = s1.ldc; d.nck1 = s1.C / 16;
     }
-    if (a->out_nchw || a->Ho != a->Hm || a->Wo != a->Wm || a->osy != 1 || a->osx != 1 || a->ooy || a->oox)
-        return WC_E_SHAPE;
-    if ((long)a->Hm * a->Wm * a->ldo * 4 >= (1L << 31) || (a->res && (long)a->Hm * a->Wm * a->ldres * 4 >= (1L << 31)))
-        return WC_E_SHAPE;
+    if (check_out_grid(a, 1, false)) return WC_E_SHAPE;
     d.B = a->B; d.H = a->Hm; d.W = a->Wm; d.N = a->N;
     d.w = w; d.bias = a->bias; d.temb = a->temb; d.temb_ld = a->temb_ld;
     d.res = a->res; d.ldres = a->ldres; d.out = a->out; d.ldo = a->ldo;
@@ -894,14 +888,7 @@ int wino_setup(const wc_conv_args* a, const void* w, int64_t w_bytes, int a_exp,
     d.abound = (res || pro == 0) ? a_bound : nullptr;
     d.wsinv = w_inv_scale;
     d.absmax = a->absmax_out;
-    d.gn_part = a->gn_part;
-    if (a->gn_part) {
-        const int sw = a->gn_sw;
-        if ((sw != 4 && sw != 8 && sw != 16 && sw != 32) || a->N % 32 || a->gn_c0 % 32 || a->gn_c0 < 0 ||
-            a->gn_c0 + a->N > a->gn_ncb * 32 || a->gn_p64 != 0 || a->gn_np64 * 64 != a->Hm * a->Wm)
-            return WC_E_SHAPE;
-        d.gn_ncb = a->gn_ncb; d.gn_sw = sw; d.gn_c0 = a->gn_c0; d.gn_np64 = a->gn_np64;
-    }
+    if (set_gn_part(d, a, a->Hm * a->Wm, false)) return WC_E_SHAPE;
     const long ntn = (a->N + BN - 1) / BN;
     if (w_bytes != ntn * (12L * d.nck0 + d.nck1) * BN * 64 || w_bytes >= (1L << 31)) return WC_E_SHAPE;
     return WC_OK;
@@ -1014,8 +1001,7 @@ extern "C" int wc_conv3x3_wino_f16x3(const wc_conv_args* a, const void* w, int64
     WDev d;
     int pro, BN;
     bool res;
-    const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN);
-    if (st != WC_OK) return st;
+    if (const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN)) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (pro == 0) return BN == 64 ? launch_wino<16, 64, 0, false>(d, s) : launch_wino<8, 128, 0, false>(d, s);
     if (BN == 64) return res ? launch_wino<16, 64, 2, true>(d, s) : launch_wino<16, 64, 2, false>(d, s);
@@ -1035,8 +1021,7 @@ extern "C" int wc_conv3x3_wino_f16x3_gnb(const wc_conv_args* a, const void* w, i
     WDev d;
     int pro, BN;
     bool res;
-    const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN);
-    if (st != WC_OK) return st;
+    if (const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN)) return st;
     if (pro != 0 || !g || !g->x || !g->sc0 || !g->sh0 || !g->part) return WC_E_ARG;
     if (g->ldx < d.N || g->splits != wc_conv3x3_wino_gnb_splits(d.N, d.H, d.W)) return WC_E_SHAPE;
     if ((long)d.B * d.H * d.W * g->ldx * 4 >= (1L << 31)) return WC_E_SHAPE;
@@ -1059,10 +1044,10 @@ extern "C" int wc_wino_vsplit_f16x3(const wc_conv_args* a, int a_exp, const floa
     const wc_conv_seg& s0 = a->seg[0];
     if (!s0.src || !s0.scale || !s0.shift || !s0.silu) return WC_E_ARG;  // the GN + SiLU segment only
     if (a->nseg == 2 && !a_bound) return WC_E_ARG;
-    if (a_exp < -60 || a_exp > 60) return WC_E_ARG;
-    if (s0.C <= 0 || s0.C % 16 || s0.ldc % 4 || (reinterpret_cast<uintptr_t>(s0.src) & 15) || s0.W % 16)
-        return WC_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(vout) & 15) || v_bytes != (int64_t)a->B * wino_vimg(s0.C, s0.H, s0.W))
+    if (!wchost::exp_ok(a_exp)) return WC_E_ARG;
+    // (plain 64-bit addressing, no SRD: the layout rule without the range)
+    if (wchost::check_src_layout(s0, 16) || s0.W % 16) return WC_E_SHAPE;
+    if (!wchost::aligned16(vout) || v_bytes != (int64_t)a->B * wino_vimg(s0.C, s0.H, s0.W))
         return WC_E_SHAPE;
     if (s0.W > 256) return WC_E_SHAPE;  // R = 256 / W rows per workgroup
     const int R = 256 / s0.W;
@@ -1093,8 +1078,7 @@ extern "C" int wc_conv3x3_wino_f16x3_vp(const wc_conv_args* a, const void* w, in
     WDev d;
     int pro, BN;
     bool res;
-    const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN);
-    if (st != WC_OK) return st;
+    if (const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN)) return st;
     if (pro != 2 || !vpre || (reinterpret_cast<uintptr_t>(vpre) & 15)) return WC_E_ARG;
     d.vimg = wino_vimg(d.C0, d.H, d.W);
     if (v_bytes != (int64_t)d.B * d.vimg || d.vimg >= (1L << 31)) return WC_E_SHAPE;
@@ -1114,8 +1098,7 @@ extern "C" int wc_conv3x3_wino_f16x3_vp8(const wc_conv_args* a, const void* w, i
     WDev d;
     int pro, BN;
     bool res;
-    const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN);
-    if (st != WC_OK) return st;
+    if (const int st = wino_setup(a, w, w_bytes, a_exp, w_inv_scale, a_bound, d, pro, res, BN)) return st;
     if (pro != 2 || !vpre || (reinterpret_cast<uintptr_t>(vpre) & 15)) return WC_E_ARG;
     if (BN != 128 || d.N % 256) return WC_E_SHAPE;
     d.vimg = wino_vimg(d.C0, d.H, d.W);

@@ -733,8 +733,7 @@ class TrainEngine:
     @staticmethod
     def _dgrad3_ok(g: View, n_out: int) -> bool:
         """The 3x3 data gradient of g (n_out output channels) fits the halo f16x3 kernel."""
-        return K.x6_eligible([Seg(g, TAPS3)], n_out, g.H, g.W) and g.C % 4 == 0 and g.ldc % 4 == 0 \
-            and g.ptr % 16 == 0
+        return K.x6_eligible([Seg(g, TAPS3)], n_out, g.H, g.W)
 
     def _dgrad3(self, g: View, c: ConvForms, f3: bool, bound, dz: View, gnb_sums: Callable):
         """dz = the 3x3 data gradient of g through c.  f3 (the f16x3 pack exists and _dgrad3_ok; bound: the per-image
@@ -897,7 +896,7 @@ class TrainEngine:
         gc, ow = self._grad_w(cur)  # the four output parities together cover every pixel
         rc = None if ow else gc
         f3t = dp.dgrad.f3t if dp.dgrad.has('f3t') else None  # packed here, also when the shape then declines it
-        if f3t is not None and K.convT4x4s2_f16x3_ok(Seg(gF, [(0, 0)]), gc.C) and gF.ptr % 16 == 0:
+        if f3t is not None and K.convT4x4s2_f16x3_ok(Seg(gF, [(0, 0)]), gc.C):
             # the ConvT of dY (same weight) in one launch on f16x3 under dY's tracked bound
             K.convT4x4s2_f16x3(Seg(gF, [(0, 0)]), f3t, None, gc, a_bound=bgF, res=rc, absmax=self._gb(cur))
             return
@@ -918,7 +917,7 @@ class TrainEngine:
         gc, ow = self._grad_w(cur)
         rc = None if ow else gc
         f3s = up.dgrad.f3s if up.dgrad.has('f3s') else None  # as f3t in _bwd_down
-        if f3s is not None and K.conv4x4s2_f16x3_ok(seg, gc.C, cur.H, cur.W) and gD.ptr % 16 == 0:
+        if f3s is not None and K.conv4x4s2_f16x3_ok(seg, gc.C, cur.H, cur.W):
             # the 4x4/s2 conv of dY on the space-to-depth halo kernel, f16x3 under dY's tracked bound
             K.conv4x4s2_f16x3(seg, f3s, None, gc, Hm=cur.H, Wm=cur.W, a_bound=bgD, res=rc, absmax=self._gb(cur))
             return

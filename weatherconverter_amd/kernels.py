@@ -164,6 +164,19 @@ class Seg:
 TAPS3 = [(dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
 
 
+def _src_view_ok(v: View, cmult: int) -> bool:
+    """The source-segment rule, check_src_seg of csrc/wc_conv_host.hpp: whole cmult-channel chunks, pixel
+    stride and base on the 16-byte grid, the whole view inside the 2 GiB buffer range."""
+    return v.C > 0 and v.C % cmult == 0 and v.ldc % 4 == 0 and v.ptr % 16 == 0 and v.B * v.H * v.W * v.ldc * 4 < 2**31
+
+
+def _res_seg_ok(s1: Seg, Hm: int, Wm: int) -> bool:
+    """The fused 1x1 residual segment of the halo kernels, check_res_seg of csrc/wc_conv_host.hpp: a raw
+    read at the output pixel itself of a view that passes _src_view_ok."""
+    return (list(s1.taps) == [(0, 0)] and s1.stride == 1 and s1.scale is None and s1.view.H == Hm and s1.view.W == Wm
+            and _src_view_ok(s1.view, 16))
+
+
 @dataclass
 class GnPart:
     """GroupNorm tile partials of one NHWC tensor (B, H, W, 32*ncb), attached to it as
@@ -710,21 +723,25 @@ def pack_wino(w: torch.Tensor, C0: int, C1: int = 0, *, device: Optional[bool] =
 
 
 def wino_eligible(segs: Sequence[Seg], N: int, Hm: int, Wm: int) -> bool:
-    """True when wc_conv3x3_wino_f16x3 accepts this conv (mirrors its host checks): segment 0 with the
-    GN+SiLU prologue (+ an optional 1x1 residual segment), or one raw segment (given a per-image bound)."""
+    """True when wc_conv3x3_wino_f16x3 accepts this conv (wino_setup in csrc/wc_wino.hip: the 3x3 stride-1
+    grid on the TH x 16 tiling, check_src_seg on each segment, check_res_seg): segment 0 with the GN+SiLU
+    prologue (+ an optional 1x1 residual segment), or one raw segment (given a per-image bound)."""
     s0 = segs[0]
     TH, _ = wino_tile(N)
-    if len(s0.taps) != 9 or s0.view.C % 16 or Hm % TH or Wm % 16 or s0.stride != 1:
-        return False
-    if list(s0.taps) != [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]:
+    if list(s0.taps) != TAPS3 or s0.stride != 1 or Hm % TH or Wm % 16 or not _src_view_ok(s0.view, 16):
         return False
     if s0.view.H != Hm or s0.view.W != Wm:
         return False
     if s0.scale is None:
         return len(segs) == 1
-    # (the 64-channel form with a residual segment runs its residual chunks as a tail phase, one barrier
-    # each: measured slower than the direct halo kernel, 1.14 vs 0.87 ms/step; it stays direct)
-    return s0.silu and (len(segs) == 1 or (segs[1].view.C % 16 == 0 and TH == 8))
+    if not s0.silu:
+        return False
+    if len(segs) == 1:
+        return True
+    s1 = segs[1]
+    # policy, not a rule of the library: the 64-channel form with a residual segment runs its residual chunks
+    # as a tail phase, one barrier each: measured slower than the direct halo kernel, 1.14 vs 0.87 ms/step
+    return _res_seg_ok(s1, Hm, Wm) and TH == 8
 
 
 @dataclass
@@ -823,15 +840,16 @@ def set_wino_vsplit(min_tiles: int) -> int:
 
 
 def wino_vsplit_wanted(segs: Sequence[Seg], N: int, Hm: int, Wm: int) -> bool:
-    """Whether the conv takes the pre-split form: the tile threshold, and every constraint
-    wc_wino_vsplit_f16x3 checks (otherwise the in-conv prologue form runs, which accepts more shapes)."""
+    """Whether the conv takes the pre-split form: the tile threshold (policy), and every constraint
+    wc_wino_vsplit_f16x3 and wc_conv3x3_wino_f16x3_vp check (otherwise the in-conv prologue form runs,
+    which accepts more shapes)."""
     s0 = segs[0]
     v = s0.view
     # the threshold weighs the redundancy the in-conv prologue pays: every output tile re-transforms the halo
     min_tiles = forms.current().wino_vp_min_tiles
     return (min_tiles > 0 and N > 64 and -(-N // 128) >= min_tiles and s0.silu
             and s0.scale is not None and Wm % 16 == 0 and Wm <= 256 and v.W == Wm and v.H == Hm
-            and v.C % 16 == 0 and v.ldc % 4 == 0 and v.ptr % 16 == 0)
+            and _src_view_ok(v, 16))
 
 
 def wino_mfma_flops(segs: Sequence[Seg], Hm: int, Wm: int, N: int, pieces: int = 3) -> float:
@@ -905,10 +923,11 @@ def pack_f16x3_convT(wt: torch.Tensor) -> X6Weight:
 
 
 def convT4x4s2_f16x3_ok(seg: Seg, N: int) -> bool:
-    """Shapes wc_convtr4x4s2_f16x3 takes (else the four implicit-GEMM parities)."""
+    """Shapes wc_convtr4x4s2_f16x3 takes (else the four implicit-GEMM parities): a raw stride-1 segment that
+    passes check_src_seg, on the TH x 16 tiling."""
     v = seg.view
     TH = x6_tile(N)[0]
-    return v.H % TH == 0 and v.W % 16 == 0 and v.C % 16 == 0 and seg.scale is None and seg.stride == 1
+    return v.H % TH == 0 and v.W % 16 == 0 and _src_view_ok(v, 16) and seg.scale is None and seg.stride == 1
 
 
 def convT4x4s2_f16x3(seg: Seg, w3: X6Weight, bias: Optional[torch.Tensor], out: View, *, a_bound: torch.Tensor,
@@ -929,10 +948,11 @@ def convT4x4s2_f16x3(seg: Seg, w3: X6Weight, bias: Optional[torch.Tensor], out: 
 
 
 def conv4x4s2_f16x3_ok(seg: Seg, N: int, Hm: int, Wm: int) -> bool:
-    """Shapes wc_conv4x4s2_f16x3 takes (else use conv_igemm_f16x3)."""
+    """Shapes wc_conv4x4s2_f16x3 takes (else use conv_igemm_f16x3): N > 64, a raw stride-2 segment that
+    passes check_src_seg, twice the 8 x 16-tiled main grid."""
     v = seg.view
     return (x6_tile(N)[1] == 128 and Hm % 8 == 0 and Wm % 16 == 0 and v.H == 2 * Hm and v.W == 2 * Wm
-            and v.C % 16 == 0 and seg.scale is None and seg.stride == 2)
+            and _src_view_ok(v, 16) and seg.scale is None and seg.stride == 2)
 
 
 def conv4x4s2_f16x3(seg: Seg, w3: X6Weight, bias: Optional[torch.Tensor], out: View, *, Hm: int, Wm: int,
@@ -974,8 +994,9 @@ def conv_igemm_f16x3_qkv(seg: Seg, w3: X6Weight, bias: Optional[torch.Tensor], q
 
 
 def proj_pa_ok(v: View, N: int) -> bool:
-    """Shapes the pre-split projection takes: HW % 128 == 0, C % 32 == 0, N % 128 == 0, aligned view."""
-    return (v.H * v.W) % 128 == 0 and v.C % 32 == 0 and N % 128 == 0 and v.ptr % 16 == 0 and v.ldc % 4 == 0
+    """Shapes the pre-split projection takes (prepare_pa in csrc/wc_igemm6.hip): HW % 128 == 0, N % 128 == 0,
+    a view of whole 32-channel chunks that passes check_src_seg."""
+    return (v.H * v.W) % 128 == 0 and N % 128 == 0 and _src_view_ok(v, 32)
 
 
 def split_f16x3_tiled(v: View, a_exp: int, scale: Optional[torch.Tensor] = None,
@@ -1055,18 +1076,15 @@ def attention_presplit_a3(qkv3: torch.Tensor, B: int, N: int, C: int, heads: int
 
 
 def x6_eligible(segs: Sequence[Seg], N: int, Hm: int, Wm: int) -> bool:
-    """True when wc_conv3x3_x6 accepts this conv (mirrors its host checks; output must be a plain
-    NHWC view on the same grid)."""
+    """True when wc_conv3x3_x6 / wc_conv3x3_f16x3 accept this conv (prepare in csrc/wc_conv6.hip: the 3x3
+    stride-1 grid on the TH x 16 tiling, check_src_seg, check_res_seg; the output must be a plain NHWC view
+    on the same grid, check_out_grid)."""
     TH, _ = x6_tile(N)
     s0 = segs[0]
     v = s0.view
-    ok = (list(s0.taps) == TAPS3 and s0.stride == 1 and v.C % 16 == 0 and v.H == Hm and v.W == Wm
-          and Hm % TH == 0 and Wm % 16 == 0 and v.B * v.H * v.W * v.ldc * 4 < 2**31)
-    if len(segs) == 2:
-        s1 = segs[1]
-        ok = ok and (list(s1.taps) == [(0, 0)] and s1.stride == 1 and s1.scale is None and s1.view.C % 16 == 0
-                     and s1.view.H == Hm and s1.view.W == Wm and s1.view.B * Hm * Wm * s1.view.ldc * 4 < 2**31)
-    return ok
+    ok = (list(s0.taps) == TAPS3 and s0.stride == 1 and _src_view_ok(v, 16) and v.H == Hm and v.W == Wm
+          and Hm % TH == 0 and Wm % 16 == 0)
+    return ok and (len(segs) == 1 or _res_seg_ok(segs[1], Hm, Wm))
 
 
 def conv3x3_x6(segs: Sequence[Seg], w6: X6Weight, bias: Optional[torch.Tensor], out: View, *, Hm: int, Wm: int,
@@ -1114,7 +1132,7 @@ def gn_partials(v: View, gp: GnPart):
 
 def gn_conv_ok(out: Optional[View], gn: Optional[GnPart], N: int, Hm: int, Wm: int, bm: Optional[int] = None) -> bool:
     """True when a split-precision conv writing `out` can emit gn's tile partials from its epilogue
-    (mirrors the host checks of wc_conv3x3_x6 / wc_conv_igemm_x6; bm = the implicit GEMM's M tile)."""
+    (set_gn_part of csrc/wc_conv_host.hpp; bm = the implicit GEMM's M tile, inside one image)."""
     return (gn is not None and out is not None and gn.covers(out) and N == out.C and N % 32 == 0
             and (Hm * Wm) % 64 == 0 and (bm is None or (Hm * Wm) % bm == 0))
 
@@ -1585,14 +1603,14 @@ def absmax_images(v: View) -> torch.Tensor:
 
 
 def wgrad3_ok(g: View, s0: Seg) -> bool:
-    """Shapes wc_conv_wgrad3 takes: segment 0 a 3x3 stride-1 grid at the gradient's own grid, M % 64,
-    C0 % 32 (% 64 when M % 128 != 0), W % 16, H % 8 (H % 2 for the 64-channel tiles)."""
+    """Shapes wc_conv_wgrad3 takes (conv_wgrad3_any in csrc/wc_wgrad3.hip): segment 0 a 3x3 stride-1 grid at
+    the gradient's own grid, M % 64, C0 % 32 (% 64 when M % 128 != 0), W % 16, H % 8 (H % 2 for the
+    64-channel tiles); the source and the gradient view each pass check_src_seg's rule."""
     v = s0.view
-    if list(s0.taps) != TAPS3 or s0.stride != 1 or v.H != g.H or v.W != g.W or g.C % 64 or g.W % 16:
+    if list(s0.taps) != TAPS3 or s0.stride != 1 or v.H != g.H or v.W != g.W or g.W % 16:
         return False
     wide = g.C % 128 == 0
-    return v.C % (32 if wide else 64) == 0 and g.H % (8 if wide else 2) == 0 and v.ldc % 4 == 0 and g.ldc % 4 == 0 \
-        and v.ptr % 16 == 0 and g.ptr % 16 == 0
+    return _src_view_ok(v, 32 if wide else 64) and _src_view_ok(g, 64) and g.H % (8 if wide else 2) == 0
 
 
 class F3Bounds(NamedTuple):
