@@ -5,12 +5,14 @@
 // below is rejected by the argument / shape validation before any launch, or is a host-only sizing
 // helper.  What it proves: the validation code reads nothing outside the caller's structs, and each
 // rejection returns the documented WC_E_* code (the Python layer turns these into RuntimeError).
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "wc_kernels.h"
 #include "wc_optim.h"
+#include "wc_sampler.h"
 
 #include "conv_args_mutations.hpp"
 
@@ -78,6 +80,28 @@ int main() {
     EXPECT(wc_ddpm_step(nullptr, p, p, p, nullptr, 1, 16, 0.f, 0.f, 1.f, 0.f, 0, 0, 0, 0, nullptr), WC_E_ARG);
     EXPECT(wc_ddpm_step(p, p, p, p, nullptr, 1, 15, 0.f, 0.f, 1.f, 0.f, 0, 0, 0, 0, nullptr), WC_E_SHAPE);
     EXPECT(wc_ddpm_step(p, p, p, p, nullptr, 1, 16, 0.f, 0.f, 1.f, 0.f, 7, 0, 0, 0, nullptr), WC_E_ARG);
+    // Strided sampling step (wc_sampler.h): null operands, noise mode, shape, scalar ranges, NaN scalars,
+    // clipping where sqrt(1 - acp_t) is 0.
+    const float qnan = std::nanf("");
+    EXPECT(wc_ddim_step(nullptr, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, nullptr, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, nullptr, p, p, 1, 16, .8f, .6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, .4f, .1f, 0, 3, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, .4f, .1f, 0, -1, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, nullptr, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, .4f, .1f, 0, WC_NOISE_TENSOR, 0, 0, 0,
+                        nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 15, .8f, .6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_SHAPE);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 0, 16, .8f, .6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_SHAPE);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, 0.f, .6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, -.6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, -.4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, .4f, -.1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, qnan, .6f, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, qnan, .9f, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, qnan, .4f, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, qnan, .1f, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, .8f, .6f, .9f, .4f, qnan, 0, 0, 0, 0, 0, nullptr), WC_E_ARG);
+    EXPECT(wc_ddim_step(p, p, p, p, nullptr, nullptr, 1, 16, 1.f, 0.f, .9f, .4f, .1f, 1, 0, 0, 0, 0, nullptr), WC_E_ARG);
     EXPECT(wc_mse_loss(nullptr, p, 16, nullptr, 1.f, nullptr, p, nullptr), WC_E_ARG);
     std::vector<double> ws(wc_mse_workspace_doubles());
     EXPECT(wc_mse_loss(p, p, 0, nullptr, 1.f, ws.data(), p, nullptr), WC_E_SHAPE);

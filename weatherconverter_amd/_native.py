@@ -33,7 +33,9 @@ AdamJob = OPTIM_ABI.structs['wc_adam_job']
 # So are the weight-averaging ones (wc_ema_update, wc_ema_swap).
 EMA_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_ema.h')).read())
 EmaJob = EMA_ABI.structs['wc_ema_job']
-_SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions, **EMA_ABI.functions}
+# And the strided sampling step (wc_ddim_step; its kernel sits beside wc_ddpm_step's in wc_misc.hip).
+SAMPLER_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_sampler.h')).read())
+_SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions, **EMA_ABI.functions, **SAMPLER_ABI.functions}
 
 _libs = {}
 _active = threading.local()

@@ -1,6 +1,7 @@
 // Small kernels of the DDPM hot path: time embedding, stem conv, scheduler step, forward
 // noising, counter-based Gaussian noise and the semantic-gradient-guidance update.
 #include "wc_common.hpp"
+#include "../../include/wc_sampler.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -440,6 +441,56 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict_
     }
 }
 
+// One DDIM transition t -> t_to (wc_sampler.h: Song et al. 2021 eq. 12 with the x0 prediction made
+// explicit, optionally clipped).  Every operation is rounded once, FP contraction pinned off and
+// sigma*z rounded before the add, as ddpm_step_kernel; the noise is ddpm_step_kernel's, bit for bit.
+// x and xo carry no __restrict__: they may be one buffer (every lane loads its vectors before it stores).
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const float* __restrict__ eps,
+                                                        const float* __restrict__ z, float* xo,
+                                                        float* __restrict__ szo, float* __restrict__ x0o,
+                                                        int64_t n4, int64_t per4, float sa, float s1m,
+                                                        float sa_to, float cdir, float sigma, int clip,
+                                                        int mode, uint64_t seed, int64_t sample0,
+                                                        int64_t step) {
+#pragma clang fp contract(off)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        f32x4 ev = reinterpret_cast<const f32x4*>(eps)[i];
+        f32x4 zv = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (mode == WC_NOISE_TENSOR) {
+            zv = reinterpret_cast<const f32x4*>(z)[i];
+        } else if (mode == WC_NOISE_PHILOX) {
+            int64_t smp = i / per4;
+            zv = normal4(seed, (uint32_t)(i - smp * per4), (uint32_t)(sample0 + smp), (uint32_t)step);
+        }
+        f32x4 r, sq, p0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float e = ev[k];
+            float x0 = __fdiv_rn(__fsub_rn(xv[k], __fmul_rn(s1m, e)), sa);
+            if (clip) {
+                const float c = x0 < -1.f ? -1.f : (x0 > 1.f ? 1.f : x0);
+                if (c != x0) {  // only where the clamp changed x0: eps consistent with the clipped x0
+                    x0 = c;
+                    e = __fdiv_rn(__fsub_rn(xv[k], __fmul_rn(sa, x0)), s1m);
+                }
+            }
+            float a = __fmul_rn(sa_to, x0), b = __fmul_rn(cdir, e);
+            asm volatile("" : "+v"(a), "+v"(b));  // both products rounded before the add
+            const float m = __fadd_rn(a, b);
+            float sz = __fmul_rn(sigma, zv[k]);
+            asm volatile("" : "+v"(sz));  // sigma*z is rounded before the add (no FMA)
+            p0[k] = x0;
+            sq[k] = sz;
+            r[k] = (szo || mode == WC_NOISE_NONE) ? m : __fadd_rn(m, sz);
+        }
+        reinterpret_cast<f32x4*>(xo)[i] = r;
+        if (szo) reinterpret_cast<f32x4*>(szo)[i] = sq;
+        if (x0o) reinterpret_cast<f32x4*>(x0o)[i] = p0;
+    }
+}
+
 __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict__ x0,
                                                         const float* __restrict__ nz,
                                                         const float* __restrict__ ca,
@@ -633,6 +684,27 @@ extern "C" int wc_ddpm_step(const float* x, const float* eps, const float* z, fl
     hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(n4, 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), x, eps, z, x_out, sz_out, n4, per_sample / 4,
                        beta, s1m, sqrt_alpha, sigma, noise_mode, seed, sample0, step);
+    WC_CHECK_LAUNCH();
+    return WC_OK;
+}
+
+extern "C" int wc_ddim_step(const float* x, const float* eps, const float* z, float* x_out, float* sz_out,
+                            float* x0_out, int64_t B, int64_t per_sample, float sqrt_acp_t,
+                            float sqrt_1m_acp_t, float sqrt_acp_to, float c_dir, float sigma, int clip_x0,
+                            int noise_mode, uint64_t seed, int64_t sample0, int64_t step, void* stream) {
+    if (!x || !eps || !x_out) return WC_E_ARG;
+    if (noise_mode < 0 || noise_mode > 2 || (noise_mode == WC_NOISE_TENSOR && !z)) return WC_E_ARG;
+    if (per_sample % 4 != 0 || per_sample < 4 || B < 1) return WC_E_SHAPE;
+    // written so that a NaN fails each test
+    if (!(sqrt_acp_t > 0.f) || !(sqrt_1m_acp_t >= 0.f) || !(c_dir >= 0.f) || !(sigma >= 0.f) ||
+        sqrt_acp_to != sqrt_acp_to)
+        return WC_E_ARG;
+    if (clip_x0 && sqrt_1m_acp_t == 0.f) return WC_E_ARG;  // the clipped elements divide by it
+    int64_t n4 = B * (per_sample / 4);
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(n4, 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), x, eps, z, x_out, sz_out, x0_out, n4,
+                       per_sample / 4, sqrt_acp_t, sqrt_1m_acp_t, sqrt_acp_to, c_dir, sigma, clip_x0 ? 1 : 0,
+                       noise_mode, seed, sample0, step);
     WC_CHECK_LAUNCH();
     return WC_OK;
 }

@@ -59,8 +59,10 @@ def gather_samples(x_local: torch.Tensor, total: int, group=None) -> torch.Tenso
 
 @torch.no_grad()
 def sample_sharded(model, scheduler, total_batch: int, im_channels: int, im_size: int, *, noise: str = 'philox',
-                   seed: int = 0, graph: bool = False, group=None, gather: bool = True) -> torch.Tensor:
-    """Reference sample loop (sample_ddpm.py:35-44) for ``total_batch`` images split over the group."""
+                   seed: int = 0, graph: bool = False, group=None, gather: bool = True, steps=None,
+                   spacing: str = 'trailing', timesteps=None, eta: float = 0.0, clip_x0: bool = False) -> torch.Tensor:
+    """Reference sample loop (sample_ddpm.py:35-44) for ``total_batch`` images split over the group.
+    ``steps`` / ``spacing`` / ``timesteps`` / ``eta`` / ``clip_x0``: strided sampling, as ``sample_tensor``."""
     from .sample_ddpm import sample_tensor
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -70,7 +72,8 @@ def sample_sharded(model, scheduler, total_batch: int, im_channels: int, im_size
         x = torch.empty((0, im_channels, im_size, im_size), dtype=torch.float32, device=dev)
         return gather_samples(x, total_batch, group) if gather else x
     x = sample_tensor(model, scheduler, count, im_channels, im_size, noise=noise, seed=seed, sample0=start,
-                      total_batch=total_batch, graph=graph)
+                      total_batch=total_batch, graph=graph, steps=steps, spacing=spacing, timesteps=timesteps, eta=eta,
+                      clip_x0=clip_x0)
     if world == 1 or not gather:
         return x
     return gather_samples(x, total_batch, group)

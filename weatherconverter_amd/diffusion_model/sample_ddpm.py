@@ -4,7 +4,9 @@ Same public functions — ``load_config``, ``sample``, ``load_model``, ``load_sc
 with the reference's argument meaning.  Differences, all opt-in or fail-loud:
   * ``sample`` returns the final x0 tensor in addition to writing the PNG grid (``save_path=None``
     skips the file), and takes build-only keywords: ``noise`` ('torch_cpu' = reference RNG stream,
-    'philox' = on-device counter-based noise), ``seed``, ``x_T``, ``graph``.
+    'philox' = on-device counter-based noise), ``seed``, ``x_T``, ``graph``; ``steps`` / ``spacing`` /
+    ``timesteps`` / ``eta`` / ``clip_x0`` sample a sub-sequence of the schedule (DDIM, ``wc_ddim_step``).
+  * ``ddim_invert`` runs the deterministic chain forwards: an image's latent at the last timestep.
   * ``load_model`` takes ``weights='ema'``: the averaged weights of a checkpoint saved with an ``EMA``.
   * ``infer`` does not swallow exceptions (reference ``:84-87`` prints and continues).
 Hot loop (reference ``:35-44``) per step: one UNet forward on the HIP engine + one fused scheduler
@@ -137,8 +139,14 @@ class _GraphStep:
 def sample_tensor(model: Unet, scheduler: LinearNoiseScheduler, batch: int, im_channels: int, im_size: int, *,
                   noise: str = 'torch_cpu', seed: Optional[int] = None, sample0: int = 0,
                   x_T: Optional[torch.Tensor] = None, graph: bool = False, total_batch: Optional[int] = None,
-                  progress=None, progress_x=None) -> torch.Tensor:
+                  progress=None, progress_x=None, steps: Optional[int] = None, spacing: str = 'trailing',
+                  timesteps=None, eta: float = 0.0, clip_x0: bool = False) -> torch.Tensor:
     """The reverse loop of reference ``sample_ddpm.py:35-44``; returns x0 (not clamped).
+
+    ``steps`` (with ``spacing``) or ``timesteps`` walk a sub-sequence tau of the schedule downwards with
+    DDIM transitions instead (``scheduler.timestep_sequence`` / ``ddim_step``; the last one is
+    tau_0 -> -1): ``eta`` = 0 is deterministic, 1 the respaced ancestral chain; ``clip_x0`` clamps the
+    x0 prediction of every step to [-1, 1].  Without them the loop is the reference's, every timestep.
 
     noise='torch_cpu': x_T and every z come from the CPU generator in the reference's order
     (``torch.randn`` of the full batch).  With ``total_batch`` > batch (sharded sampling) every
@@ -147,6 +155,9 @@ def sample_tensor(model: Unet, scheduler: LinearNoiseScheduler, batch: int, im_c
     """
     dev = scheduler.device
     T = scheduler.num_timesteps
+    tau = None
+    if steps is not None or timesteps is not None:
+        tau = scheduler.timestep_sequence(steps, spacing=spacing, timesteps=timesteps)
     shape = (batch, im_channels, im_size, im_size)
     full = total_batch or batch
     full_shape = (full, im_channels, im_size, im_size)
@@ -170,6 +181,9 @@ def sample_tensor(model: Unet, scheduler: LinearNoiseScheduler, batch: int, im_c
     ts = torch.arange(T, device=dev, dtype=torch.long)
     runner = _GraphStep(model, xt) if graph else None
     nxt = torch.empty_like(xt)
+    if tau is not None:
+        return _strided_loop(model, scheduler, runner, xt, nxt, ts, tau, eta, clip_x0, noise, seed, sample0,
+                             full_shape, progress, progress_x)
     # reference-RNG mode: the per-step z draws (the full-batch CPU tensor, in the reference's order)
     # run one step ahead on a worker thread while the GPU computes the UNet.  They come from a private
     # generator that continues the global CPU generator's state, and the global state is set to the
@@ -211,15 +225,88 @@ def sample_tensor(model: Unet, scheduler: LinearNoiseScheduler, batch: int, im_c
     return xt
 
 
+def _strided_loop(model, scheduler, runner, xt, nxt, ts, tau, eta, clip_x0, noise, seed, sample0, full_shape,
+                  progress, progress_x):
+    """sample_tensor's loop over the sub-sequence tau (ascending), walked downwards: per step one UNet
+    forward at the timestep being left and one eager wc_ddim_step launch after it (the captured UNet
+    graph is _GraphStep's, unchanged).  Reference-RNG mode keeps sample_tensor's guarantee: one
+    full-batch draw per step with sigma > 0, in loop order, from a private generator one step ahead of
+    the GPU, and the global generator is left where those draws end."""
+    dev, batch = scheduler.device, xt.shape[0]
+    hops = [(tau[k], tau[k - 1] if k > 0 else -1) for k in reversed(range(len(tau)))]
+    noisy = [scheduler.ddim_scalars(t, t_to, eta)[4] > 0.0 for t, t_to in hops]
+    pool = fut = gen = None
+    left = sum(noisy)  # CPU draws still to submit
+    if noise == 'torch_cpu' and left:
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(1)
+        gen = torch.Generator()
+        gen.set_state(torch.get_rng_state())
+
+        def cpu_draw():
+            return torch.randn(full_shape, generator=gen)[sample0:sample0 + batch].contiguous()
+
+        fut = pool.submit(cpu_draw)
+        left -= 1
+    try:
+        for (t, t_to), has_z in zip(hops, noisy):
+            t_dev = ts[t:t + 1]
+            eps = runner(xt, t_dev) if runner is not None else model(xt, t_dev)
+            z = None
+            if has_z and noise == 'torch_cpu':
+                z = fut.result().to(dev)
+                if left:
+                    fut = pool.submit(cpu_draw)
+                    left -= 1
+            scheduler.ddim_step(xt, eps, t, t_to, out=nxt, eta=eta, clip_x0=clip_x0, z=z, noise=noise, seed=seed,
+                                sample0=sample0)
+            xt, nxt = nxt, xt
+            if progress is not None:
+                progress(t)
+            if progress_x is not None:  # (timestep left, x after the step)
+                progress_x(t, xt)
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True)
+        if gen is not None:
+            torch.set_rng_state(gen.get_state())
+    return xt
+
+
+@torch.no_grad()
+def ddim_invert(model: Unet, scheduler: LinearNoiseScheduler, x0: torch.Tensor, *, steps: Optional[int] = None,
+                spacing: str = 'trailing', timesteps=None, graph: bool = False) -> torch.Tensor:
+    """DDIM inversion (Song et al. 2021, the eta = 0 chain run forwards): encodes the image batch x0
+    into its latent at the last timestep of tau, deterministically.  tau is walked upwards: eps from
+    the UNet at the timestep being left, then the transition to the next larger one (sigma = 0).  The
+    image itself is taken as x at tau_0.  Sampling that latent back with the same tau and eta = 0
+    reproduces the image up to the discretisation error of the two chains."""
+    dev = scheduler.device
+    tau = scheduler.timestep_sequence(steps, spacing=spacing, timesteps=timesteps)
+    xt = x0.to(dev, torch.float32).contiguous().clone()
+    ts = torch.arange(scheduler.num_timesteps, device=dev, dtype=torch.long)
+    runner = _GraphStep(model, xt) if graph else None
+    nxt = torch.empty_like(xt)
+    for t, t_to in zip(tau, tau[1:]):
+        t_dev = ts[t:t + 1]
+        eps = runner(xt, t_dev) if runner is not None else model(xt, t_dev)
+        scheduler.ddim_step(xt, eps, t, t_to, out=nxt, eta=0.0)
+        xt, nxt = nxt, xt
+    return xt
+
+
 def sample(model, scheduler: LinearNoiseScheduler, train_config: TrainingConfig, model_config: ModelConfig,
            diffusion_config: DiffusionConfig, save_path: Optional[str] = 'diffusion_model_v2/outputs/samples', *,
            noise: str = 'torch_cpu', seed: Optional[int] = None, x_T: Optional[torch.Tensor] = None,
-           graph: bool = False) -> torch.Tensor:
-    """Reference ``sample`` (:23-53): T-step reverse loop, clamp, [0,1], PNG grid.  Returns x0."""
+           graph: bool = False, steps: Optional[int] = None, spacing: str = 'trailing', timesteps=None,
+           eta: float = 0.0, clip_x0: bool = False) -> torch.Tensor:
+    """Reference ``sample`` (:23-53): T-step reverse loop, clamp, [0,1], PNG grid.  Returns x0.
+    ``steps`` / ``spacing`` / ``timesteps`` / ``eta`` / ``clip_x0``: strided sampling, as ``sample_tensor``."""
     if diffusion_config.num_timesteps != scheduler.num_timesteps:
         raise RuntimeError('scheduler / diffusion_config timestep mismatch')
     xt = sample_tensor(model, scheduler, train_config.sample_size, model_config.im_channels, model_config.im_size,
-                       noise=noise, seed=seed, x_T=x_T, graph=graph)
+                       noise=noise, seed=seed, x_T=x_T, graph=graph, steps=steps, spacing=spacing, timesteps=timesteps,
+                       eta=eta, clip_x0=clip_x0)
     if save_path is not None:
         ims = (torch.clamp(xt, -1., 1.).detach().cpu() + 1) / 2
         grid = make_grid(ims, nrow=train_config.num_grid_rows)

@@ -1350,6 +1350,32 @@ def ddpm_step(x: torch.Tensor, eps: torch.Tensor, out: torch.Tensor, beta: float
                  sqrt_alpha, sigma, mode, seed & ((1 << 64) - 1), sample0, step, _stream())
 
 
+def ddim_step(x: torch.Tensor, eps: torch.Tensor, out: torch.Tensor, sqrt_acp_t: float, sqrt_1m_acp_t: float,
+              sqrt_acp_to: float, c_dir: float, sigma: float, *, clip_x0: bool = False,
+              z: Optional[torch.Tensor] = None, mode: int = _native.NOISE_NONE, seed: int = 0, sample0: int = 0,
+              step: int = 0, sz_out: Optional[torch.Tensor] = None, x0_out: Optional[torch.Tensor] = None):
+    """One DDIM transition t -> t_to (include/wc_sampler.h wc_ddim_step); `out` may be `x` itself."""
+    def dev_f32(v, what):  # the kernel reads / writes float4 vectors of device memory
+        _req(v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.data_ptr() % 16 == 0,
+             f'ddim_step {what}: contiguous 16-byte-aligned fp32 device tensor')
+
+    _req(x.shape == eps.shape == out.shape, 'ddim_step shapes')
+    for v, what in ((x, 'x'), (eps, 'eps'), (out, 'out')):
+        dev_f32(v, what)
+    if mode == _native.NOISE_TENSOR:
+        _req(z is not None and z.shape == x.shape, 'noise tensor shape')
+        dev_f32(z, 'z')
+    B = x.shape[0]
+    per = x.numel() // B
+    for v, what in ((sz_out, 'sz_out'), (x0_out, 'x0_out')):
+        if v is not None:
+            _req(v.shape == x.shape, f'{what} shape')
+            dev_f32(v, what)
+    _native.call('wc_ddim_step', x.data_ptr(), eps.data_ptr(), _ptr(z), out.data_ptr(), _ptr(sz_out), _ptr(x0_out), B,
+                 per, sqrt_acp_t, sqrt_1m_acp_t, sqrt_acp_to, c_dir, sigma, int(bool(clip_x0)), mode,
+                 seed & ((1 << 64) - 1), sample0, step, _stream())
+
+
 def add_noise(x0: torch.Tensor, noise: torch.Tensor, coef_a: torch.Tensor, coef_b: torch.Tensor) -> torch.Tensor:
     _req(x0.shape == noise.shape and x0.is_contiguous() and noise.is_contiguous(), 'add_noise shapes')
     _req(x0.is_cuda and noise.is_cuda and x0.dtype == torch.float32 and noise.dtype == torch.float32

@@ -11,6 +11,10 @@ Per reverse step i (N = 500 over the T = 1000 schedule, lambda = 60):
 ``mode='applied'`` keeps the guided xt on guided steps.  D2 (``mu + None`` TypeError at i = 0) is not
 reproduced: the last step returns ``mu`` as ``sample_ddpm`` does.  LCG runs only when ``use_lcg``
 (the reference's LCG crashes, D3; see ``sgg.apply_lcg``).
+
+``steps=`` walks a sub-sequence tau of [0, N) instead (``timestep_sequence`` with N in place of T), with
+(mu, sigma*z) from ``scheduler.ddim_prev_timestep``; GSG runs where the position k of tau is odd and LCG
+on even k, which at stride 1 is the parity of i above.
 """
 from typing import Optional
 
@@ -47,11 +51,19 @@ class _Replay:
 def sample_with_sgg(input_tensor: torch.Tensor, diff_model, diff_scheduler, seg_model, gt: torch.Tensor,
                     srgan_model, *, LAMBDA: float = 60.0, N: int = 500, mode: str = 'applied', use_lcg: bool = False,
                     t_start: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                    progress=None, return_latent: bool = False, graph: bool = True):
+                    progress=None, return_latent: bool = False, graph: bool = True, steps: Optional[int] = None,
+                    spacing: str = 'trailing', eta: float = 1.0, clip_x0: bool = False):
     """graph=True replays the UNet and SRGAN forwards from HIP graphs (same kernels, same results);
-    the segmenter's autograd pass stays eager."""
+    the segmenter's autograd pass stays eager.  steps=: DDIM transitions over `steps` of the N timesteps
+    (eta = 1: the respaced ancestral chain; the guidance scales with sigma, so eta = 0 is refused)."""
     if mode not in ('reference', 'applied'):
         raise ValueError("mode must be 'reference' or 'applied'")
+    tau = None
+    if steps is not None:
+        from .diffusion_model.scheduler.linear_noise_scheduler import timestep_sequence
+        tau = timestep_sequence(N, steps, spacing=spacing)
+        if not eta > 0:
+            raise ValueError('sample_with_sgg: the strided guided loop needs eta > 0 (sigma = 0 means no guidance)')
     dev = diff_scheduler.device
     x0 = input_tensor.to(dev, torch.float32)
     # forward process (translation.py:63-65): random t in [0, N), one noising of the input
@@ -64,15 +76,21 @@ def sample_with_sgg(input_tensor: torch.Tensor, diff_model, diff_scheduler, seg_
         from .diffusion_model.sample_ddpm import _GraphStep
         unet_run = _GraphStep(diff_model, xt)
         sr_run = _Replay(lambda v: srgan_inference(srgan_model, v), xt)
-    for i in reversed(range(N)):
+    # the reference's loop visits every i of [0, N) as hop i -> i - 1 at position k = i
+    hops = [(i, i - 1, i) for i in reversed(range(N))] if tau is None else \
+        [(tau[k], tau[k - 1] if k > 0 else -1, k) for k in reversed(range(len(tau)))]
+    for i, i_to, k in hops:
         eps = unet_run(xt, ts[i:i + 1]) if unet_run is not None else diff_model(xt, ts[i:i + 1])
-        mu, sigma, _ = diff_scheduler.sample_prev_timestep(xt, eps, i)
-        if i == 0:
+        if tau is None:
+            mu, sigma, _ = diff_scheduler.sample_prev_timestep(xt, eps, i)
+        else:
+            mu, sigma, _ = diff_scheduler.ddim_prev_timestep(xt, eps, i, i_to, eta=eta, clip_x0=clip_x0)
+        if k == 0:
             xt = mu
             break
         sr_xt = sr_run(xt) if sr_run is not None else srgan_inference(srgan_model, xt)
         guided = None
-        if i % 2 == 1:
+        if k % 2 == 1:
             guided = apply_gsg(seg_model, mu, sigma, sr_xt, gt, LAMBDA)
         elif use_lcg:
             guided = apply_lcg(seg_model, mu, sigma, sr_xt, gt, LAMBDA, mode=mode)
