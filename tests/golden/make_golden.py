@@ -11,6 +11,8 @@ weatherconverter_amd/synthetic.py, so only outputs + digests are stored):
   unet_tiny.npz         tiny-config Unet forward, B=2, shared t and per-sample t
   unet_64.npz           64-px default-config Unet forward, B=2 (config 1 model)
   unet_256.npz          256-px default-config Unet forward, B=1 (BASELINE architecture)
+  unet_128.npz          128-px default-config Unet forward, B=1 (config.yaml's own im_size; --only-128 writes
+                        this file alone)
   traj_64_T50.npz       config 1: 64 px, B=2, T=50 reverse trajectory (sample_ddpm.py:35-44 loop)
   traj_64_T1000.npz     64 px default config, B=1, the full T=1000 schedule, same loop and RNG stream
                         (--only-traj1000; ~5 min on 8 CPU threads)
@@ -87,6 +89,7 @@ def main():
     ap.add_argument('--only-guided', action='store_true')
     ap.add_argument('--only-old', action='store_true')
     ap.add_argument('--only-traj1000', action='store_true')
+    ap.add_argument('--only-128', action='store_true', help='write unet_128.npz alone')
     ap.add_argument('--only-sched-steps', action='store_true',
                     help='add the reverse-step vectors at STEP_T / STEP2_T to the existing sched.npz')
     args = ap.parse_args()
@@ -111,6 +114,8 @@ def main():
     from diffusion_model.models.unet_base import Unet, get_time_embedding
     from diffusion_model.scheduler.linear_noise_scheduler import LinearNoiseScheduler
 
+    if args.only_128:
+        return unet_128(Unet, default_model(ref_models, 128))
     out = {}
     # ------------------------------------------------------------- manifest
     manifest = {}
@@ -146,14 +151,7 @@ def main():
 
     # ------------------------------------------------------------- UNet forwards
     def run_forward(mc, B, t, xseed, wseed=0):
-        net = Unet(mc)
-        sd = synthetic_state_dict(net.state_dict(), seed=wseed)
-        net.load_state_dict(sd)
-        net.eval()
-        x = synthetic_images((B, mc.im_channels, mc.im_size, mc.im_size), seed=xseed)
-        with torch.no_grad():
-            y = net(x, torch.as_tensor(t))
-        return net, y, state_dict_digest(sd)
+        return _run_forward(Unet, mc, B, t, xseed, wseed)
 
     net, y1, dg = run_forward(cfgs['tiny'], 2, [7], 101)
     _, y2, _ = run_forward(cfgs['tiny'], 2, [3, 900], 102)
@@ -165,6 +163,7 @@ def main():
     _, y256, dg256 = run_forward(cfgs['default_256'], 1, [611], 301)
     np.savez(os.path.join(HERE, 'unet_256.npz'), y=y256.numpy(), digest=dg256)
     print('256 done', float(y256.abs().max()))
+    unet_128(Unet, cfgs['default_128'])
 
     # ------------------------------------------------------------- config-1 trajectory
     if not args.skip_traj:
@@ -185,6 +184,24 @@ def main():
                 xt = mean + sigma if i != 0 else mean
         np.savez(os.path.join(HERE, 'traj_64_T50.npz'), x0=xt.numpy(), eps_first=eps_first.numpy(), seed=3455)
         print('traj done', float(xt.abs().max()))
+
+
+def _run_forward(Unet, mc, B, t, xseed, wseed=0):
+    net = Unet(mc)
+    sd = synthetic_state_dict(net.state_dict(), seed=wseed)
+    net.load_state_dict(sd)
+    net.eval()
+    x = synthetic_images((B, mc.im_channels, mc.im_size, mc.im_size), seed=xseed)
+    with torch.no_grad():
+        y = net(x, torch.as_tensor(t))
+    return net, y, state_dict_digest(sd)
+
+
+def unet_128(Unet, mc):
+    """The reference's own training size (config.yaml im_size 128), B=1, one t, as unet_256.npz."""
+    _, y128, dg128 = _run_forward(Unet, mc, 1, [433], 401)
+    np.savez(os.path.join(HERE, 'unet_128.npz'), y=y128.numpy(), digest=dg128)
+    print('128 done', float(y128.abs().max()))
 
 
 def traj1000(args):

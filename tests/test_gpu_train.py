@@ -567,9 +567,14 @@ def test_device_pack_equals_torch_pack_bf16_line(N, C0, C1, ntaps, order, res_f1
 
 
 # ------------------------------------------------------------------ whole model
-def _model_grads(mc, B, precision, seed=0):
+_REF_GRADS = {}  # share_ref: (config, B, seed, t) -> (oracle float64 grads, loss)
+
+
+def _model_grads(mc, B, precision, seed=0, t=None, share_ref=False):
     """(our grads, oracle float64 grads, loss ours, loss ref) for one MSE training iteration;
-    precision 'f16' = the 16-bit training line (set_train_precision)."""
+    precision 'f16' = the 16-bit training line (set_train_precision).  t: the per-sample timesteps
+    (int64 [B]; drawn from the seeded generator when None).  share_ref: compute the oracle's gradients
+    (they do not depend on the precision) once per (config, B, seed, t) and keep them, unchanged."""
     import sys
     from conftest import ROOT
     sys.path.insert(0, ROOT)
@@ -588,16 +593,23 @@ def _model_grads(mc, B, precision, seed=0):
     S = mc.im_size
     x = torch.randn((B, mc.im_channels, S, S), generator=g)
     noise = torch.randn((B, mc.im_channels, S, S), generator=g)
-    t = torch.randint(0, 1000, (B, ), generator=g)
+    t_drawn = torch.randint(0, 1000, (B, ), generator=g)
+    t = t_drawn if t is None else t
+    assert t.shape == (B, ) and t.dtype == torch.int64
     pred = net(x.cuda(), t.cuda())
     loss = torch.nn.MSELoss()(pred, noise.cuda())
     loss.backward()
     ours = {k: p.grad.detach().cpu().double() for k, p in net.named_parameters()}
-    ref_pred = unet_forward(sd, mc, x.double(), t)
-    ref_loss = torch.nn.MSELoss()(ref_pred, noise.double())
-    ref_loss.backward()
-    ref = {k: sd[k].grad for k in ours}
-    return ours, ref, float(loss), float(ref_loss)
+    key = (mc.model_dump_json(), B, seed, tuple(t.tolist()))
+    if not share_ref or key not in _REF_GRADS:
+        ref_pred = unet_forward(sd, mc, x.double(), t)
+        ref_loss = torch.nn.MSELoss()(ref_pred, noise.double())
+        ref_loss.backward()
+        if not share_ref:
+            return ours, {k: sd[k].grad for k in ours}, float(loss), float(ref_loss)
+        _REF_GRADS[key] = ({k: sd[k].grad for k in ours}, float(ref_loss.detach()))
+    ref, ref_loss = _REF_GRADS[key]
+    return ours, ref, float(loss), ref_loss
 
 
 def _check(ours, ref, per_tensor=1e-4, overall=1e-5):

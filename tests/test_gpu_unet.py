@@ -63,6 +63,28 @@ def test_unet_256_baseline_architecture(precision):
     assert rel_l2(y.cpu(), g['y']) < 1e-5
 
 
+@pytest.mark.parametrize('precision', ['f16x3', 'bf16x6', 'fp32'])
+def test_unet_128_reference_config(precision):
+    """The reference's own model (config.yaml: im_size 128, trained at B = 4): the golden input alone against
+    the reference's forward, then as row 0 of a B = 4 batch beside three other inputs -- bit-equal to the
+    singleton run, the batch finite."""
+    from weatherconverter_amd.synthetic import state_dict_digest
+    mc, net = _model('default_128', precision=precision)
+    g = np.load(os.path.join(GOLDEN, 'unet_128.npz'))
+    assert mc.im_size == 128 and state_dict_digest(net.state_dict()) == str(g['digest'])
+    x0 = _x(mc, 1, 401)
+    xb = torch.cat([x0, _x(mc, 3, 402)]).cuda()
+    t = torch.tensor([433]).cuda()
+    with torch.no_grad():
+        y = net(x0.cuda(), t)
+        yb = net(xb, t)
+    err = rel_l2(y.cpu(), g['y'])
+    print(f'unet 128 {precision}: rel-L2 vs the reference {err:.3e}')
+    assert err < 1e-5
+    assert yb.shape == (4, 3, 128, 128) and bool(torch.isfinite(yb).all())
+    assert torch.equal(yb[:1], y)
+
+
 def test_unet_256_batch16_rows_match_singletons():
     """Full BASELINE batch (B=16 at 256 px): each row equals the same sample run alone."""
     mc, net = _model('default_256')

@@ -96,6 +96,11 @@ def test_oracle_unet_256():
     assert _forward_case('default_256', 'unet_256.npz', 'y', 1, [611], 301) <= _bound()
 
 
+def test_oracle_unet_128():
+    """The reference's own training size (config.yaml im_size = 128)."""
+    assert _forward_case('default_128', 'unet_128.npz', 'y', 1, [433], 401) <= _bound()
+
+
 @pytest.mark.slow
 def test_oracle_trajectory_config1():
     """Config 1 (64 px, B=2, T=50) trajectory through the restated loop (sample_ddpm.py:35-44)."""
