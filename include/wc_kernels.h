@@ -588,7 +588,12 @@ int wc_attention_bwd6(const float* qkv, int ld_qkv, const float* out, int ld_out
 /* The same backward on f16x3 (two round-to-nearest fp16 pieces per operand, three products per block):
  * Q, K, V scaled by 2^eq, 2^ek, 2^ev — the training forward's exponents from the in-projection bounds
  * (|Q| 2^eq <= 2^14 ...); dO by 2^edo from dobound[b] = per-image max |dO| (device, wc_absmax_images);
- * P by 2^14; dS by 2^eds with the bound |dS| <= 2 d max|dO| max|V|.  Head dim in {32, 64, 128}, or 192
+ * P by 2^14; dS = P (dP - D) by 2^eds under a proven bound: with row_work (device, optional, [2 B] float32
+ * zeroed by the caller) the call first raises row_work[b] and row_work[B + b] to the per-image max per-head
+ * row norms of dO and V, and |dS| <= 2 max||dO_i|| max||V_j|| (Cauchy-Schwarz on dP = dO_i . V_j and
+ * D = dO_i . O_i, O_i a convex combination of V rows); with NULL, |dS| <= 2 d max|dO| 2^(14 - ev), the
+ * forward's static bound on max|V|, which is far looser and costs dQ / dK three to four digits at
+ * N >= 1024.  Head dim in {32, 64, 128}, or 192
  * (dQ on f16x3; dK / dV on f16x3 with the V rows in LDS when dqkv_absmax is given, on fp32 MFMA, which
  * raises no bound, when it is NULL: the caller's choice is the one argument, no environment switch).
  * dqkv_absmax (optional, [B], caller-zeroed): raised to the max |dqkv| written per image. */
@@ -600,7 +605,7 @@ int wc_attention_bwd_dkdv192(const float* qkv, int ld_qkv, const float* dout, in
 int wc_attention_bwd_f16x3(const float* qkv, int ld_qkv, const float* out, int ld_out, const float* dout,
                            int ld_dout, const float* lse, float* dv_work, float* dqkv, int ld_dqkv, int B, int N,
                            int C, int heads, float scale, int eq, int ek, int ev, const float* dobound,
-                           float* dqkv_absmax, void* stream);
+                           float* row_work, float* dqkv_absmax, void* stream);
 /* Its first step alone: dv_work[(b*heads + h)*N + q] = sum_d dout[b, q, h*D + d] * out[b, q, h*D + d]. */
 int wc_attention_bwd_prep(const float* out, int ld_out, const float* dout, int ld_dout, int B, int N, int heads,
                           int D, float* dv_work, void* stream);

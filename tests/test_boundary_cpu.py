@@ -145,6 +145,7 @@ def test_envelope_constants_repeat_the_native_host_checks():
         assert sorted(int(n) for n in re.findall(r'case\s+(\d+)', m.group(1))) == split
     assert list(K.ATTN_BWD_DIMS) == _cases(_csrc('wc_attention_bwd.hip'), 'extern "C" int wc_attention_bwd(')
     assert set(K.ATTN_BWD_DIMS) == set(K.ATTN_FWD_DIMS)  # whatever runs forward also trains
+    assert list(K.ATTN_BWD_F3_DIMS) == _cases(_csrc('wc_attention_bwd6.hip'), 'static int attention_bwd_split(')
     assert all(d % 8 == 0 for d in K.ATTN_BWD_DIMS)  # BwdCfg: DH = D / 2 read four floats at a time
     assert re.search(r'constexpr int BK = (\d+);', _csrc('wc_conv.hip')).group(1) == str(K.IGEMM_BK)
     misc = _csrc('wc_misc.hip')

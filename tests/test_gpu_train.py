@@ -612,12 +612,31 @@ def _model_grads(mc, B, precision, seed=0, t=None, share_ref=False):
     return ours, ref, float(loss), ref_loss
 
 
+def _grad_errors(ours, ref):
+    """{name: rel-L2} of every gradient tensor, and of the q, k and v row blocks of every attention
+    in-projection gradient as tensors of their own ('name[q]' ...): with a diffuse softmax the q and k rows
+    are far smaller than the v rows, so an error in them (the f16x3 attention backward's dS) hides under the
+    per-tensor bound of the whole in_proj_weight.  The k block of in_proj_bias is exactly zero in exact
+    arithmetic (a constant added to every key moves no softmax: sum_j dS_ij = 0), so its error is measured
+    against the norm of the whole bias gradient, as the per-tensor check always measured it."""
+    errs = {k: rel_l2(ours[k], ref[k]) for k in ref}
+    for k in ref:
+        if k.endswith(('in_proj_weight', 'in_proj_bias')):
+            c = ref[k].shape[0] // 3
+            for i, n in enumerate('qkv'):
+                a, b = ours[k][i * c:(i + 1) * c], ref[k][i * c:(i + 1) * c]
+                zero = n == 'k' and k.endswith('in_proj_bias')
+                errs[f'{k}[{n}]'] = float((a - b).norm() / ref[k].norm()) if zero else rel_l2(a, b)
+    return errs
+
+
 def _check(ours, ref, per_tensor=1e-4, overall=1e-5):
-    worst = sorted(((rel_l2(ours[k], ref[k]), k) for k in ref), reverse=True)
+    worst = sorted(((e, k) for k, e in _grad_errors(ours, ref).items()), reverse=True)
     a = torch.cat([ours[k].flatten() for k in ref])
     b = torch.cat([ref[k].flatten() for k in ref])
     tot = rel_l2(a, b)
     print(f'overall grad rel-L2 {tot:.3e}; worst tensors {worst[:4]}')
+    print('worst in-projection q / k blocks', [w for w in worst if w[1].endswith(('[q]', '[k]'))][:4])
     assert all(ours[k].shape == ref[k].shape for k in ref)
     assert tot < overall, tot
     assert worst[0][0] < per_tensor, worst[:4]

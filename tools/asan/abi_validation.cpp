@@ -144,12 +144,12 @@ int main() {
     EXPECT(wc_conv_wgrad_f16x3(&wg, p, 1, p, 0, nullptr, nullptr, nullptr), WC_E_ARG);  // segment 1 unbounded
     EXPECT(wc_wgrad_reduce(nullptr, 1, 4, 4, 4, 4, 4, p, 0, 0, 0, nullptr, 0, 0, nullptr), WC_E_ARG);
     EXPECT(wc_wgrad_reduce(p, 1, 4, 8, 4, 4, 4, p, 0, 0, 0, nullptr, 0, 0, nullptr), WC_E_ARG);  // dw1 missing
-    EXPECT(wc_attention_bwd_f16x3(p, 96, p, 32, p, 32, p, p, p, 96, 1, 64, 32, 4, 1.f, 0, 0, 0, nullptr, nullptr,
-                                  nullptr), WC_E_ARG);  // no dO bound
-    EXPECT(wc_attention_bwd_f16x3(p, 96, p, 32, p, 32, p, p, p, 96, 1, 64, 32, 4, 1.f, 99, 0, 0, p, nullptr, nullptr),
-           WC_E_ARG);  // exponent out of range
-    EXPECT(wc_attention_bwd_f16x3(p, 96, p, 32, p, 32, p, p, p, 96, 1, 64, 30, 4, 1.f, 0, 0, 0, p, nullptr, nullptr),
-           WC_E_SHAPE);  // heads do not divide C
+    EXPECT(wc_attention_bwd_f16x3(p, 96, p, 32, p, 32, p, p, p, 96, 1, 64, 32, 4, 1.f, 0, 0, 0, nullptr, p, nullptr,
+                                  nullptr), WC_E_ARG);  // no dO bound (the row-norm workspace does not replace it)
+    EXPECT(wc_attention_bwd_f16x3(p, 96, p, 32, p, 32, p, p, p, 96, 1, 64, 32, 4, 1.f, 99, 0, 0, p, nullptr, nullptr,
+                                  nullptr), WC_E_ARG);  // exponent out of range
+    EXPECT(wc_attention_bwd_f16x3(p, 96, p, 32, p, 32, p, p, p, 96, 1, 64, 30, 4, 1.f, 0, 0, 0, p, p, nullptr,
+                                  nullptr), WC_E_SHAPE);  // heads do not divide C
     EXPECT(wc_attention_bwd_dkdv192(p, 96, p, 32, p, p, p, 96, 1, 64, 32, 4, 1.f, nullptr), WC_E_SHAPE);  // D != 192
     EXPECT(wc_attention_bwd6(nullptr, 96, p, 32, p, 32, p, p, p, 96, 1, 64, 32, 4, 1.f, nullptr), WC_E_ARG);
     EXPECT(wc_gn_bwd_apply(nullptr, 4, p, 4, p, p, nullptr, nullptr, 1, p, 1, 16, 4, p, 4, 0, p, nullptr), WC_E_ARG);

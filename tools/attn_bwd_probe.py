@@ -31,12 +31,15 @@ def main():
     K.attention_fwd_lse(qkv, o, lse, B, N, C, H, precision='f16x3', exps=exps)
     dob = do.abs().reshape(B, -1).amax(1)
     dqkv = torch.empty_like(qkv)
-    K.attention_bwd(qkv, o, do, lse, dqkv, B, N, C, H, precision='f16x3', exps=exps, dout_bound=dob)
+    rw = torch.zeros(2 * B, device=dev)  # the row-norm workspace, as the training engine passes it
+    K.attention_bwd(qkv, o, do, lse, dqkv, B, N, C, H, precision='f16x3', exps=exps, dout_bound=dob,
+                        row_work=rw)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(a.reps):
-        K.attention_bwd(qkv, o, do, lse, dqkv, B, N, C, H, precision='f16x3', exps=exps, dout_bound=dob)
+        K.attention_bwd(qkv, o, do, lse, dqkv, B, N, C, H, precision='f16x3', exps=exps, dout_bound=dob,
+                        row_work=rw)
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / a.reps

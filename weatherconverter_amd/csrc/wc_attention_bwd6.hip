@@ -25,11 +25,20 @@
 // two and split into two round-to-nearest fp16 pieces, products h*h + h*l + l*h on
 // v_mfma_f32_32x32x16_f16 (3 MFMAs per block instead of 6).  The exponents come from range bounds:
 // Q, K, V from the forward's in-projection bounds (eq, ek, ev: |Q| 2^eq <= 2^14 ...); dO from its
-// per-image absmax (dobound[b], |dO| 2^edo < 2^14); P in [0, 1] at 2^14; dS = P (dP - D) with
-// |dP_ij| = |dO_i . V_j| <= d max|dO| max|V| and |D_i| = |dO_i . O_i| <= d max|dO| max|V| (O is a
-// convex combination of V rows), so |dS| < 2^(e_do + 2 + log2 d + 14 - ev) and
-// eds = ev - e_do - 2 - log2 d puts it below 2^14 (e_do = floor(log2 max|dO|)).  Accumulators carry
-// the products' power-of-two factors, removed exactly before use / in the epilogue.
+// per-image absmax (dobound[b], |dO| 2^edo < 2^14); P in [0, 1] at 2^14; dS = P (dP - D), dP_ij = dO_i . V_j,
+// D_i = dO_i . O_i with O_i a convex combination of V rows, under one of two proven bounds:
+//   measured (row_work given: rownorm_max_kernel raises it to the per-image max per-head row norms of dO and V):
+//     |dP_ij| <= ||dO_i|| ||V_j|| and |D_i| <= ||dO_i|| max_j ||V_j|| (Cauchy-Schwarz), so
+//     |dS| <= 2 max_i ||dO_i|| max_j ||V_j|| < 2^(fo + fv + 3) with fo, fv the floor(log2) of the two norms,
+//     and eds = 11 - fo - fv puts it below 2^14 (the fp32 rounding of the norms, ~d 2^-24, is covered by the
+//     factor 4 between 2^14 and fp16's largest value);
+//   static (NULL): |dP_ij|, |D_i| <= d max|dO| max|V| with max|V| <= 2^(14 - ev), the forward's bound, so
+//     |dS| < 2^(e_do + 2 + log2 d + 14 - ev), eds = ev - e_do - 2 - log2 d (e_do = floor(log2 max|dO|)).
+// The static bound is the row-L1 worst case of the in-projection, ~2^11 above the values the UNet's layers
+// hold, d max max a further ~2^8 above a dot product, and P ~ 1/N: under it the scaled dS of the 1024- and
+// 4096-token layers lies below the smallest normal fp16, keeps 5 to 7 bits, and dQ / dK are 1e-3 .. 1e-2 off
+// float64 (tests/test_gpu_attn_regimes.py); the training engine passes the measured norms.  Accumulators
+// carry the products' power-of-two factors, removed exactly before use / in the epilogue.
 #include "wc_x6.hpp"
 
 namespace {
@@ -219,7 +228,8 @@ struct BwdScales {
     int eq = 0, ek = 0, ev = 0, edo = 0, eds = 0, ep = 0;
 };
 template <int D, bool F3>
-WC_DEVICE BwdScales bwd_scales(int eq, int ek, int ev, const float* dobound, int b) {
+WC_DEVICE BwdScales bwd_scales(int eq, int ek, int ev, const float* dobound, const float* dorow, const float* vrow,
+                               int b) {
     BwdScales r;
     if constexpr (F3) {
         constexpr int LOGD = D == 32 ? 5 : D == 64 ? 6 : D == 128 ? 7 : 8;
@@ -228,7 +238,16 @@ WC_DEVICE BwdScales bwd_scales(int eq, int ek, int ev, const float* dobound, int
         if (m > 0.f) {
             const int e = (int)((__float_as_uint(m) >> 23) & 0xffu) - 127;  // floor(log2 max|dO|)
             edo = min(60, 13 - e);
-            eds = min(60, ev - e - 2 - LOGD);
+            // |dS| <= 2 max_i ||dO_i|| max_j ||V_j|| < 2^(fo + fv + 3) (Cauchy-Schwarz on the measured per-head row
+            // norms; a zero V norm means dP = D = 0, so dS = 0 at any scale), else the static bound on max|V|
+            if (dorow) {
+                const float rv = vrow[b];
+                const int fo = (int)((__float_as_uint(dorow[b]) >> 23) & 0xffu) - 127;
+                const int fv = (int)((__float_as_uint(rv) >> 23) & 0xffu) - 127;
+                eds = rv > 0.f ? min(60, 11 - fo - fv) : 60;
+            } else {
+                eds = min(60, ev - e - 2 - LOGD);
+            }
         }
         r.eq = eq; r.ek = ek; r.ev = ev; r.edo = max(edo, -100); r.eds = max(eds, -100); r.ep = 14;
         r.sq = ldexpf(1.f, eq); r.sk = ldexpf(1.f, ek); r.sv = ldexpf(1.f, ev);
@@ -247,7 +266,8 @@ template <int D, bool F3, int DS = 1, bool VL = false>
 __global__ __launch_bounds__(256, F3 && WC_SINGLE16 && D <= 64 ? 2 : 1) void attn_bwd6_dkdv_kernel(
     const float* __restrict__ qkv, int ldq, const float* __restrict__ dO, int lddo, const float* __restrict__ lse,
     const float* __restrict__ Dv, float* __restrict__ dqkv, int lddq, int N, int C, float scale_log2, float scale,
-    int eq, int ek, int ev, const float* __restrict__ dobound, float* __restrict__ amx) {
+    int eq, int ek, int ev, const float* __restrict__ dobound, const float* __restrict__ dorow,
+    const float* __restrict__ vrow, float* __restrict__ amx) {
     using Cf = B6Cfg<D, F3>;
     constexpr int NP = Cf::NP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // 2 stages: Q, dO tiles, lse, Dv
@@ -262,7 +282,7 @@ __global__ __launch_bounds__(256, F3 && WC_SINGLE16 && D <= 64 ? 2 : 1) void att
     static_assert(Cf::NDB % DS == 0, "DS divides the 32-dim output blocks");
     const int db0 = (int)(blockIdx.x % DS) * NDBP;
     const int key = (int)(blockIdx.x / DS) * 128 + wave * 32 + l32;
-    const BwdScales sc = bwd_scales<D, F3>(eq, ek, ev, dobound, b);
+    const BwdScales sc = bwd_scales<D, F3>(eq, ek, ev, dobound, dorow, vrow, b);
     const float s_log2 = scale_log2 * ldexpf(1.f, -(sc.eq + sc.ek));  // S carries 2^(eq + ek)
     const float dp_un = ldexpf(1.f, -(sc.edo + sc.ev));               // dP carries 2^(edo + ev)
 
@@ -407,7 +427,8 @@ template <int D, bool F3, int DS = 1>
 __global__ __launch_bounds__(256, F3 && WC_SINGLE16 && D <= 128 ? 2 : 1) void attn_bwd6_dq_kernel(
     const float* __restrict__ qkv, int ldq, const float* __restrict__ dO, int lddo, const float* __restrict__ lse,
     const float* __restrict__ Dv, float* __restrict__ dqkv, int lddq, int N, int C, float scale_log2, float scale,
-    int eq, int ek, int ev, const float* __restrict__ dobound, float* __restrict__ amx) {
+    int eq, int ek, int ev, const float* __restrict__ dobound, const float* __restrict__ dorow,
+    const float* __restrict__ vrow, float* __restrict__ amx) {
     using Cf = B6Cfg<D, F3>;
     constexpr int NP = Cf::NP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // 2 stages: K, V tiles
@@ -422,7 +443,7 @@ __global__ __launch_bounds__(256, F3 && WC_SINGLE16 && D <= 128 ? 2 : 1) void at
     static_assert(Cf::NDB % DS == 0, "DS divides the 32-dim output blocks");
     const int db0 = (int)(blockIdx.x % DS) * NDBP;
     const int qme = (int)(blockIdx.x / DS) * 128 + wave * 32 + l32;
-    const BwdScales sc = bwd_scales<D, F3>(eq, ek, ev, dobound, b);
+    const BwdScales sc = bwd_scales<D, F3>(eq, ek, ev, dobound, dorow, vrow, b);
     const float s_log2 = scale_log2 * ldexpf(1.f, -(sc.eq + sc.ek));
     const float dp_un = ldexpf(1.f, -(sc.edo + sc.ev));
 
@@ -514,7 +535,7 @@ __global__ __launch_bounds__(256, F3 && WC_SINGLE16 && D <= 128 ? 2 : 1) void at
 template <int D, bool F3, int DS = 1>
 int launch_bwd6(const float* qkv, int ldq, const float* dO, int lddo, const float* lse, const float* Dv, float* dqkv,
                 int lddq, int B, int N, int C, int heads, float scale, int eq, int ek, int ev, const float* dobound,
-                float* amx, hipStream_t s) {
+                const float* dorow, const float* vrow, float* amx, hipStream_t s) {
     using Cf = B6Cfg<D, F3>;
     static bool attr_set = false;
     if (!attr_set) {
@@ -530,11 +551,54 @@ int launch_bwd6(const float* qkv, int ldq, const float* dO, int lddo, const floa
     const float scale_log2 = scale * 1.4426950408889634f;
     WC_SET_NAME("attn_bwd6_dkdv_kernel", {WC_TI(D), WC_TB(F3), WC_TI(DS)});
     hipLaunchKernelGGL((attn_bwd6_dkdv_kernel<D, F3, DS>), grid, dim3(256), Cf::LDS, s, qkv, ldq, dO, lddo, lse, Dv, dqkv,
-                       lddq, N, C, scale_log2, scale, eq, ek, ev, dobound, amx);
+                       lddq, N, C, scale_log2, scale, eq, ek, ev, dobound, dorow, vrow, amx);
     WC_CHECK_LAUNCH();
     WC_SET_NAME("attn_bwd6_dq_kernel", {WC_TI(D), WC_TB(F3), WC_TI(DS)});
     hipLaunchKernelGGL((attn_bwd6_dq_kernel<D, F3, DS>), grid, dim3(256), Cf::LDS, s, qkv, ldq, dO, lddo, lse, Dv, dqkv,
-                       lddq, N, C, scale_log2, scale, eq, ek, ev, dobound, amx);
+                       lddq, N, C, scale_log2, scale, eq, ek, ev, dobound, dorow, vrow, amx);
+    WC_CHECK_LAUNCH();
+    return WC_OK;
+}
+
+// rmax[b] = max over the rows n and heads h of image b of the Euclidean norm of x[b][n][h D .. h D + D) (rows at
+// pitch ldx); the caller zeroes rmax.  Grid (row chunks, B); 8 lanes share a (row, head): lane l sums the
+// float4s l, l + 8, ... of its D / 4 (coalesced 128-byte segments), the eight partial sums meet in three
+// butterflies; one atomic per workgroup (norms >= 0 order like their bits, so the max is exact and order-free).
+__global__ __launch_bounds__(256) void rownorm_max_kernel(const float* __restrict__ x, int ldx, int N, int heads, int D,
+                                                         int rpb, float* __restrict__ rmax) {
+    const int b = blockIdx.y;
+    const int r0 = (int)blockIdx.x * rpb;
+    const int nitems = (min(N, r0 + rpb) - r0) * heads;
+    const float* img = x + ((long)b * N + r0) * ldx;
+    const int l8 = threadIdx.x & 7, slot = threadIdx.x >> 3;
+    float m = 0.f;
+    for (int base = 0; base < nitems; base += 32) {  // the same trip count for every thread
+        const int it = base + slot;
+        float s = 0.f;
+        if (it < nitems) {
+            const float* q = img + (long)(it / heads) * ldx + (it % heads) * D + 4 * l8;
+            for (int j = 0; j < D / 32; ++j) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(q + 32 * j);
+                s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            }
+        }
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 4, 64);
+        m = fmaxf(m, s);
+    }
+    block_absmax_atomic(rmax, b, sqrtf(m));
+}
+
+// row_work[b] and row_work[B + b]: the per-image max per-head row norms of dO and of V (D % 32 == 0).
+int launch_rownorms(const float* qkv, int ld_qkv, const float* dout, int ld_dout, int B, int N, int C, int heads,
+                    float* row_work, hipStream_t s) {
+    const int rpb = 64;  // rows per workgroup
+    const dim3 grid((unsigned)((N + rpb - 1) / rpb), (unsigned)B);
+    hipLaunchKernelGGL(rownorm_max_kernel, grid, dim3(256), 0, s, dout, ld_dout, N, heads, C / heads, rpb, row_work);
+    WC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rownorm_max_kernel, grid, dim3(256), 0, s, qkv + 2 * C, ld_qkv, N, heads, C / heads, rpb,
+                       row_work + B);
     WC_CHECK_LAUNCH();
     return WC_OK;
 }
@@ -554,7 +618,7 @@ extern "C" int wc_attention_bwd_dkdv192(const float* qkv, int ld_qkv, const floa
 template <int DS>
 int launch_dkdv192(const float* qkv, int ld_qkv, const float* dout, int ld_dout, const float* lse, const float* dv_work,
                    float* dqkv, int ld_dqkv, int B, int N, int C, int heads, float scale, int eq, int ek, int ev,
-                   const float* dobound, float* amx, hipStream_t s) {
+                   const float* dobound, const float* dorow, const float* vrow, float* amx, hipStream_t s) {
     using Cf = B6Cfg<192, true>;
     static bool attr_set = false;
     if (!attr_set) {
@@ -566,7 +630,7 @@ int launch_dkdv192(const float* qkv, int ld_qkv, const float* dout, int ld_dout,
     WC_SET_NAME("attn_bwd6_dkdv_kernel", {WC_TI(192), WC_TB(true), WC_TI(DS), WC_TB(true)});
     hipLaunchKernelGGL((attn_bwd6_dkdv_kernel<192, true, DS, true>), dim3((N + 127) / 128 * DS, heads, B), dim3(256),
                        Cf::LDS_VL, s, qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, N, C,
-                       scale * 1.4426950408889634f, scale, eq, ek, ev, dobound, amx);
+                       scale * 1.4426950408889634f, scale, eq, ek, ev, dobound, dorow, vrow, amx);
     WC_CHECK_LAUNCH();
     return WC_OK;
 }
@@ -574,7 +638,7 @@ int launch_dkdv192(const float* qkv, int ld_qkv, const float* dout, int ld_dout,
 static int attention_bwd_split(const float* qkv, int ld_qkv, const float* out, int ld_out, const float* dout,
                                int ld_dout, const float* lse, float* dv_work, float* dqkv, int ld_dqkv, int B, int N,
                                int C, int heads, float scale, bool f3, int eq, int ek, int ev, const float* dobound,
-                               float* amx, void* stream) {
+                               float* row_work, float* amx, void* stream) {
     if (!qkv || !out || !dout || !lse || !dv_work || !dqkv || (f3 && !dobound)) return WC_E_ARG;
     if (heads <= 0 || C % heads || B <= 0 || N <= 0) return WC_E_SHAPE;
     if (ld_qkv % 4 || ld_out % 4 || ld_dout % 4 || ld_dqkv % 4 || ld_qkv < 3 * C || ld_dqkv < 3 * C || ld_out < C ||
@@ -587,11 +651,18 @@ static int attention_bwd_split(const float* qkv, int ld_qkv, const float* out, i
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int st = wc_attention_bwd_prep(out, ld_out, dout, ld_dout, B, N, heads, D, dv_work, stream);
     if (st != WC_OK) return st;
+    // the measured bounds of dS (f16x3, every head dim below is a multiple of 32)
+    const float* dorow = f3 ? row_work : nullptr;
+    const float* vrow = dorow ? row_work + B : nullptr;
+    if (dorow && (D == 32 || D == 64 || D == 128 || D == 192)) {
+        st = launch_rownorms(qkv, ld_qkv, dout, ld_dout, B, N, C, heads, row_work, s);
+        if (st != WC_OK) return st;
+    }
 #define WC_BWD6(DD)                                                                                                    \
     (f3 ? launch_bwd6<DD, true>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, eq, ek, \
-                                ev, dobound, amx, s)                                                                   \
+                                ev, dobound, dorow, vrow, amx, s)                                                      \
         : launch_bwd6<DD, false>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, 0, 0, \
-                                 0, nullptr, amx, s))
+                                 0, nullptr, nullptr, nullptr, amx, s))
     switch (D) {
         case 32: return WC_BWD6(32);
         case 64: return WC_BWD6(64);
@@ -609,7 +680,7 @@ static int attention_bwd_split(const float* qkv, int ld_qkv, const float* out, i
             // instead of 2 (dK / dV) and 3 (dQ) times
             if (!fp32_dkdv) {
                 st = launch_dkdv192<1>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale, eq,
-                                       ek, ev, dobound, amx, s);
+                                       ek, ev, dobound, dorow, vrow, amx, s);
                 if (st != WC_OK) return st;
                 static bool attr1 = false;
                 if (!attr1) {
@@ -621,7 +692,7 @@ static int attention_bwd_split(const float* qkv, int ld_qkv, const float* out, i
                 WC_SET_NAME("attn_bwd6_dq_kernel", {WC_TI(192), WC_TB(true), WC_TI(1)});
                 hipLaunchKernelGGL((attn_bwd6_dq_kernel<192, true, 1>), dim3((N + 127) / 128, heads, B), dim3(256), Cf::LDS,
                                    s, qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, N, C,
-                                   scale * 1.4426950408889634f, scale, eq, ek, ev, dobound, amx);
+                                   scale * 1.4426950408889634f, scale, eq, ek, ev, dobound, dorow, vrow, amx);
                 WC_CHECK_LAUNCH();
                 return WC_OK;
             }
@@ -643,13 +714,14 @@ static int attention_bwd_split(const float* qkv, int ld_qkv, const float* out, i
                 // output dims in two workgroups (DS = 2: no scratch; one workgroup spilled 216 B/lane and
                 // was no faster, removed)
                 st = launch_dkdv192<2>(qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads, scale,
-                                       eq, ek, ev, dobound, amx, s);
+                                       eq, ek, ev, dobound, dorow, vrow, amx, s);
                 if (st != WC_OK) return st;
             }
             WC_SET_NAME("attn_bwd6_dq_kernel", {WC_TI(192), WC_TB(true), WC_TI(3)});
             hipLaunchKernelGGL((attn_bwd6_dq_kernel<192, true, 3>), dim3((N + 127) / 128 * 3, heads, B), dim3(256),
                                Cf::LDS, s, qkv, ld_qkv, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, N, C, scale_log2,
-                               scale, eq, ek, ev, dobound, fp32_dkdv ? nullptr : amx);
+                               scale, eq, ek, ev, dobound, dorow, vrow,
+                               fp32_dkdv ? nullptr : amx);
             WC_CHECK_LAUNCH();
             return WC_OK;
         }
@@ -662,15 +734,17 @@ extern "C" int wc_attention_bwd6(const float* qkv, int ld_qkv, const float* out,
                                  int ld_dout, const float* lse, float* dv_work, float* dqkv, int ld_dqkv, int B, int N,
                                  int C, int heads, float scale, void* stream) {
     return attention_bwd_split(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads,
-                               scale, false, 0, 0, 0, nullptr, nullptr, stream);
+                               scale, false, 0, 0, 0, nullptr, nullptr, nullptr, stream);
 }
 
 // f16x3 form: eq / ek / ev the forward's exponents of Q, K, V (|Q| 2^eq <= 2^14 ...), dobound[B] the
-// per-image max |dO| (device memory); dqkv_absmax (optional, [B]) raised to the max |dqkv| written.
+// per-image max |dO| (device memory); row_work (optional, [2 B], caller-zeroed): raised to the per-image max
+// per-head row norms of dO ([b]) and V ([B + b]) that then scale dS, else the static bound 2^(14 - ev) on
+// max |V| does; dqkv_absmax (optional, [B]) raised to the max |dqkv| written.
 extern "C" int wc_attention_bwd_f16x3(const float* qkv, int ld_qkv, const float* out, int ld_out, const float* dout,
                                       int ld_dout, const float* lse, float* dv_work, float* dqkv, int ld_dqkv, int B,
                                       int N, int C, int heads, float scale, int eq, int ek, int ev,
-                                      const float* dobound, float* dqkv_absmax, void* stream) {
+                                      const float* dobound, float* row_work, float* dqkv_absmax, void* stream) {
     return attention_bwd_split(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, dv_work, dqkv, ld_dqkv, B, N, C, heads,
-                               scale, true, eq, ek, ev, dobound, dqkv_absmax, stream);
+                               scale, true, eq, ek, ev, dobound, row_work, dqkv_absmax, stream);
 }

@@ -407,15 +407,16 @@ class TrainEngine:
             K.GnPart.attach(t, sw)
         return t
 
-    def _zrow(self, B: int) -> torch.Tensor:
+    def _zrow(self, B: int, n: int = 1) -> torch.Tensor:
         """A zeroed float32[B] on the device (a per-image bound that writers raise): rows of one pooled
-        zero fill instead of a fill launch each.  A row is never handed out twice."""
+        zero fill instead of a fill launch each; n > 1: n rows as one float32[n * B].  A row is never
+        handed out twice."""
         pool = getattr(self, '_zpool', None)
-        if pool is None or pool.shape[1] != B or self._zi >= pool.shape[0]:
+        if pool is None or pool.shape[1] != B or self._zi + n > pool.shape[0]:
             self._zpool = pool = torch.zeros((128, B), dtype=torch.float32, device=self.device)
             self._zi = 0
-        self._zi += 1
-        return pool[self._zi - 1]
+        self._zi += n
+        return pool[self._zi - 1] if n == 1 else pool[self._zi - n:self._zi].view(-1)
 
     def _gview(self, v: View) -> View:
         """The gradient view of a forward view, allocated on first use but NOT yet zeroed: a gradient
@@ -860,11 +861,13 @@ class TrainEngine:
         bgq = None
         args = (*(t.view(B * N, -1) for t in (qkv, o, do)), lse, dqkv.view(B * N, 3 * C), B, N, C, ap.heads)
         if f3a:
-            # f16x3 under the forward's Q / K / V exponents and the per-image max |dO|; the kernels raise
-            # the per-image max |dqkv| as they write it (head dims 32 / 64 / 128)
+            # f16x3 under the forward's Q / K / V exponents and the per-image max |dO|; dS under the per-image
+            # row norms of dO and V the call measures into row_work (the static bound behind exps[2] is ~2^11
+            # above the values: scaled by it dS falls into fp16's subnormals at N >= 1024); the kernels raise the
+            # per-image max |dqkv| as they write it (head dims 32 / 64 / 128)
             bgq = self._zrow(B)
             if not K.attention_bwd(*args, precision='f16x3', exps=exps, dout_bound=self._bound(View.full(do), bdo),
-                                   dqkv_absmax=bgq):
+                                   dqkv_absmax=bgq, row_work=self._zrow(B, 2)):
                 bgq = None
         else:
             K.attention_bwd(*args, precision=self.precision)

@@ -23,6 +23,7 @@ from .forms import CONV_PRECISIONS, wino_vp_wide  # noqa: F401  (kernels.wino_vp
 ATTN_FWD_DIMS = (8, 16, 24, 32, 48, 64, 96, 128, 160, 192)  # wc_attention.hip: attention_fwd_any
 ATTN_SPLIT_DIMS = (32, 64, 96, 128, 160, 192)  # wc_attention6.hip: the split-precision forward (head dim % 32 == 0)
 ATTN_BWD_DIMS = (8, 16, 24, 32, 48, 64, 96, 128, 160, 192)  # wc_attention_bwd.hip: wc_attention_bwd
+ATTN_BWD_F3_DIMS = (32, 64, 128, 192)  # wc_attention_bwd6.hip: attention_bwd_split with f3 (wc_attention_bwd_f16x3)
 IGEMM_BK = 32  # wc_conv.hip: channels per K-step of the fp32 implicit GEMM (every segment's C % BK == 0)
 SPLIT_CK = 16  # channels per K-step of the split-precision packs (pack_x6 / pack_f16x3: C % 16 == 0)
 GN_GROUPS = 8  # the model's GroupNorm(8, C)
@@ -1227,6 +1228,27 @@ def attention_exps_from_norms(l1: torch.Tensor, babs: torch.Tensor, gamma_absmax
     return tuple(exps)
 
 
+def attention_bwd_exps(d: int, ev: int, dout_absmax: float,
+                       row_norms: Optional[Tuple[float, float]] = None) -> Tuple[int, int, int]:
+    """(edo, eds, ep): the power-of-two exponents wc_attention_bwd_f16x3 gives dO, dS and P of one image
+    (bwd_scales in csrc/wc_attention_bwd6.hip, mirrored here).  |dO| 2^edo < 2^14 from e = floor(log2 max|dO|);
+    P in [0, 1] at 2^14; dS = P (dP - D) under row_norms = (max per-head row norm of dO, of V):
+    |dS| <= 2 max||dO_i|| max||V_j|| < 2^(fo + fv + 3) (Cauchy-Schwarz), eds = 11 - fo - fv; without them under
+    the forward's static bound max|V| <= 2^(14 - ev): |dS| <= 2 d max|dO| max|V|, eds = ev - e - 2 - ceil(log2 d).
+    Either way |dS| 2^eds < 2^14."""
+    import math
+    _req(d in ATTN_BWD_F3_DIMS, f'f16x3 attention backward: head dims {ATTN_BWD_F3_DIMS}')
+    if not dout_absmax > 0:
+        return 60, 60, 14
+    e = math.frexp(dout_absmax)[1] - 1
+    if row_norms is not None:
+        ro, rv = (float(x) for x in row_norms)
+        eds = 11 - (math.frexp(ro)[1] - 1) - (math.frexp(rv)[1] - 1) if rv > 0 else 60
+    else:
+        eds = ev - e - 2 - {32: 5, 64: 6, 128: 7, 192: 8}[d]
+    return max(min(60, 13 - e), -100), max(min(60, eds), -100), 14
+
+
 def temb(t: torch.Tensor, w1, b1, w2, b2, proj_w, proj_b) -> torch.Tensor:
     _req(t.dtype == torch.int64 and t.is_cuda and t.dim() == 1, 'timesteps must be a 1-D int64 device tensor')
     nt = t.shape[0]
@@ -1619,11 +1641,14 @@ def noise_embed(noise: torch.Tensor, ang: torch.Tensor, out: View):
 
 # ---- UNet backward (csrc/wc_backward.hip, csrc/wc_attention_bwd.hip) ----
 
-def absmax_images(v: View) -> torch.Tensor:
-    """float32[B]: max |x| over each image of the view (wc_absmax_images)."""
+def absmax_images(v: View, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32[B]: max |x| over each image of the view (wc_absmax_images); out: a zeroed float32[B] to
+    raise instead of a fresh one."""
     v.check()
     _req(v.C % 4 == 0 and v.ldc % 4 == 0 and v.ptr % 16 == 0, 'absmax view: C % 4, 16-byte aligned')
-    out = torch.zeros((v.B, ), dtype=torch.float32, device=v.t.device)
+    if out is None:
+        out = torch.zeros((v.B, ), dtype=torch.float32, device=v.t.device)
+    _req(_bound_ok(out, v.B), 'absmax output: float32 [B] on the device')
     _timed('absmax_images_kernel', 'wc_absmax_images', 0.0, v.ptr, v.ldc, v.B, v.H * v.W, v.C, out.data_ptr(), _stream())
     return out
 
@@ -1886,12 +1911,17 @@ def attention_fwd_lse(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, B
 
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, dqkv: torch.Tensor,
                   B: int, N: int, C: int, heads: int, precision: str = 'fp32', exps: Optional[Tuple[int, int, int]] = None,
-                  dout_bound: Optional[torch.Tensor] = None, dqkv_absmax: Optional[torch.Tensor] = None) -> bool:
+                  dout_bound: Optional[torch.Tensor] = None, dqkv_absmax: Optional[torch.Tensor] = None,
+                  row_work: Optional[torch.Tensor] = None) -> bool:
     """d qkv (same [q | k | v] rows as qkv) of softmax(Q K^T / sqrt(d)) V from the forward's output and lse:
     fp32 MFMA (wc_attention_bwd: head dims ATTN_BWD_DIMS), or with precision 'bf16x6' / 'f16x3' and a head dim in {32, 64, 128}
     (f16x3 also 192) the split-precision kernels: f16x3 (wc_attention_bwd_f16x3) when the Q / K / V exponents of the
     forward (exps) and the per-image max |dout| (dout_bound, device float32 [B]) are given, else
-    bf16x6 (wc_attention_bwd6).  dqkv_absmax: float32 [B] raised to the max |dqkv| written per image
+    bf16x6 (wc_attention_bwd6).  row_work: zeroed device float32 [2 B] that the f16x3 call raises to the
+    per-image max per-head row norms of dout ([:B]) and of V ([B:]) and scales dS under (attention_bwd_exps);
+    without it the kernels fall back to the forward's static bound 2^(14 - exps[2]) on max |V|, which costs
+    dQ / dK three to four digits at N >= 1024.
+    dqkv_absmax: float32 [B] raised to the max |dqkv| written per image
     by the f16x3 kernels; returns whether it was (else the caller measures the bound itself)."""
     for t_, w in ((qkv, 3 * C), (out, C), (dout, C), (dqkv, 3 * C)):
         _req(t_.is_cuda and t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == B * N * w,
@@ -1902,6 +1932,8 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
             dqkv.data_ptr(), 3 * C, B, N, C, heads, float(d**-0.5))
     f = forms.current()
     f3ok = precision == 'f16x3' and exps is not None and dout_bound is not None and f.attn_bwd_f16x3
+    if f3ok and row_work is not None:
+        _req(_bound_ok(row_work, 2 * B), 'row_work: float32 [2 B] on the device')
     if d == 192 and f3ok and f.attn_bwd6:
         # dQ on f16x3 with the output dims in three parts; dK / dV on f16x3 with the V rows in LDS (or, with
         # forms.attn_bwd192_fp32, on fp32 MFMA, which raises no bound: the C side follows the dqkv_absmax
@@ -1911,7 +1943,7 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
         if amx is not None:
             _req(_bound_ok(amx, B), 'dqkv_absmax: float32 [B] on the device')
         _timed(f'attention_bwd<{d}>', 'wc_attention_bwd_f16x3', 10.0 * B * N * N * C, *args, int(exps[0]),
-               int(exps[1]), int(exps[2]), dout_bound.data_ptr(), _ptr(amx), _stream())
+               int(exps[1]), int(exps[2]), dout_bound.data_ptr(), _ptr(row_work), _ptr(amx), _stream())
         return amx is not None
     if precision != 'fp32' and d in (32, 64, 128) and f.attn_bwd6:
         if f3ok:
@@ -1920,7 +1952,8 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
             if dqkv_absmax is not None:
                 _req(_bound_ok(dqkv_absmax, B), 'dqkv_absmax: float32 [B] on the device')
             _timed(f'attention_bwd<{d}>', 'wc_attention_bwd_f16x3', 10.0 * B * N * N * C, *args, int(exps[0]),
-                   int(exps[1]), int(exps[2]), dout_bound.data_ptr(), _ptr(dqkv_absmax), _stream())
+                   int(exps[1]), int(exps[2]), dout_bound.data_ptr(), _ptr(row_work), _ptr(dqkv_absmax),
+                   _stream())
             return dqkv_absmax is not None
         _timed(f'attention_bwd<{d}>', 'wc_attention_bwd6', 10.0 * B * N * N * C, *args, _stream())
         return False
