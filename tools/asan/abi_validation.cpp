@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "wc_data.h"
 #include "wc_kernels.h"
 #include "wc_optim.h"
 #include "wc_sampler.h"
@@ -124,6 +125,73 @@ int main() {
     if (wc_optim_chunk_elems() <= 0 || wc_optim_chunk_elems() % 4 != 0 || sizeof(wc_adam_job) % 8 != 0) {
         std::printf("FAIL wc_optim_chunk_elems / wc_adam_job size\n");
         ++failures;
+    }
+
+    // Training-input kernel (wc_data.h): the host copy of the job table is read, its pointers never are.
+    // A 40 x 30 image to S = 64 (resized 85 x 64, ksize 3 on both axes), the whole image uploaded.
+    {
+        wc_augment_job good;
+        std::memset(&good, 0, sizeof(good));
+        good.src = good.hbounds = good.hcoefs = good.vbounds = good.vcoefs = reinterpret_cast<const int*>(p);
+        good.pitch = 120;
+        good.rect_w = good.img_w = 40;
+        good.rect_h = good.img_h = 30;
+        good.out_w = 85;
+        good.out_h = 64;
+        good.ksize_h = good.ksize_v = 3;
+        good.crop_x = 10;
+        float* out16 = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15));
+        EXPECT(wc_augment_batch(nullptr, &good, 1, 64, out16, nullptr), WC_E_ARG);
+        EXPECT(wc_augment_batch(&good, nullptr, 1, 64, out16, nullptr), WC_E_ARG);
+        EXPECT(wc_augment_batch(&good, &good, 1, 64, nullptr, nullptr), WC_E_ARG);
+        EXPECT(wc_augment_batch(&good, &good, 0, 64, out16, nullptr), WC_E_ARG);
+        EXPECT(wc_augment_batch(&good, &good, 1, 64, out16 + 1, nullptr), WC_E_ARG);  // misaligned out
+        EXPECT(wc_augment_batch(&good, &good, 1, 2, out16, nullptr), WC_E_SHAPE);
+        EXPECT(wc_augment_batch(&good, &good, 1, 62, out16, nullptr), WC_E_SHAPE);
+        wc_augment_job j = good;
+        j.src = nullptr;
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_ARG);
+        j = good;
+        j.vcoefs = nullptr;
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_ARG);
+        j = good;
+        j.ksize_h = 1;
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_SHAPE);
+        j.ksize_h = 4;
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_SHAPE);
+        j.ksize_h = 5;  // odd, but not this geometry's
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_SHAPE);
+        j = good;
+        j.crop_x = 22;  // 85 - 64 = 21 is the last origin
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_SHAPE);
+        j = good;
+        j.rect_x = 5;  // the window at crop_x = 10 reads source columns [4, 36)
+        j.rect_w = 31;
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_SHAPE);
+        j = good;
+        j.pitch = 119;
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_SHAPE);
+        j = good;
+        j.flip = 2;
+        EXPECT(wc_augment_batch(&j, &good, 1, 64, out16, nullptr), WC_E_SHAPE);
+        wc_augment_job two[2] = {good, good};
+        two[1].out_h = 63;
+        EXPECT(wc_augment_batch(two, &good, 2, 64, out16, nullptr), WC_E_SHAPE);
+        // one output row that does not fit a workgroup's LDS: refused, there is no CPU path
+        j = good;
+        j.img_w = j.img_h = j.out_w = j.out_h = j.rect_w = j.rect_h = 16000;
+        j.pitch = 48000;
+        j.crop_x = 0;
+        EXPECT(wc_augment_batch(&j, &good, 1, 16000, out16, nullptr), WC_E_SHAPE);
+        int64_t first = -1, count = -1;
+        EXPECT(wc_resample_span(40, 85, 10, 74, &first, &count), WC_OK);
+        if (first != 4 || count != 32) {
+            std::printf("FAIL wc_resample_span -> [%lld, +%lld)\n", (long long)first, (long long)count);
+            ++failures;
+        }
+        EXPECT(wc_resample_span(40, 85, 10, 10, &first, &count), WC_E_SHAPE);
+        EXPECT(wc_resample_span(40, 85, 0, 86, &first, &count), WC_E_SHAPE);
+        EXPECT(wc_resample_span(40, 85, 0, 85, nullptr, &count), WC_E_ARG);
     }
 
     // Round-3 training entry points: weight gradients, split-precision attention backward, bounds.

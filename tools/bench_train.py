@@ -110,6 +110,33 @@ DTYPES = {
 }
 
 
+def train_iteration(net, opt, sched, crit, images, noise, t, *, clip=None, after_step=None, ev=None):
+    """One training iteration (train_ddpm.py:94-114) on device tensors; returns the detached loss.  clip: called
+    between backward and opt.step() (clip_grad_norm_ with a torch optimizer); after_step: called after
+    opt.step() (the weight average); ev: five timing events, recorded after the forward [0], the backward
+    [1], the optimizer step [2] and after_step [4] ([3] is the caller's, before the iteration).  Shared with
+    tools/bench_input.py, which feeds it from the loader."""
+    opt.zero_grad(set_to_none=True)
+    noisy = sched.add_noise(images, noise, t)
+    pred = net(noisy, t)
+    loss = crit(pred, noise)
+    if ev:
+        ev[0].record()
+    loss.backward()
+    if ev:
+        ev[1].record()
+    if clip is not None:
+        clip()
+    opt.step()
+    if ev:
+        ev[2].record()
+    if after_step is not None:
+        after_step()
+    if ev:
+        ev[4].record()
+    return loss.detach()
+
+
 def train_step(args):
     from weatherconverter_amd import kernels
     from weatherconverter_amd.diffusion_model.config import model_config
@@ -144,29 +171,20 @@ def train_step(args):
     noises = [kernels.philox_normal((B, 3, S, S), dev, args.seed, step=i) for i in range(nb)]
     ts = [torch.randint(0, 1000, (B, ), generator=g).to(dev) for _ in range(nb)]
 
-    def step(i, ev=None):
-        opt.zero_grad(set_to_none=True)
-        noisy = sched.add_noise(imgs[i % nb], noises[i % nb], ts[i % nb])
-        pred = net(noisy, ts[i % nb])
-        loss = crit(pred, noises[i % nb])
-        if ev:
-            ev[0].record()
-        loss.backward()
-        if ev:
-            ev[1].record()
-        if args.max_grad_norm is not None and args.optimizer == 'torch':
-            torch.nn.utils.clip_grad_norm_(params, args.max_grad_norm)  # train_ddpm.py:112
-        opt.step()
-        if ev:
-            ev[2].record()
+    def clip():
+        torch.nn.utils.clip_grad_norm_(params, args.max_grad_norm)  # train_ddpm.py:112
+
+    def average():
         if args.ema == 'wc':
             ema.update()
-        elif args.ema == 'torch':
+        else:
             with torch.no_grad():
                 torch._foreach_lerp_(shadows, params, 1.0 - ema_decay)
-        if ev:
-            ev[4].record()
-        return loss.detach()
+
+    def step(i, ev=None):
+        return train_iteration(net, opt, sched, crit, imgs[i % nb], noises[i % nb], ts[i % nb],
+                               clip=clip if args.max_grad_norm is not None and args.optimizer == 'torch' else None,
+                               after_step=average if args.ema != 'none' else None, ev=ev)
 
     for i in range(args.warmup):
         step(i)

@@ -35,7 +35,11 @@ EMA_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_ema.h')).read(
 EmaJob = EMA_ABI.structs['wc_ema_job']
 # And the strided sampling step (wc_ddim_step; its kernel sits beside wc_ddpm_step's in wc_misc.hip).
 SAMPLER_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_sampler.h')).read())
-_SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions, **EMA_ABI.functions, **SAMPLER_ABI.functions}
+# And the training-input kernel (wc_augment_batch: Pillow-exact resize, crop, flip and normalisation).
+DATA_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_data.h')).read())
+AugmentJob = DATA_ABI.structs['wc_augment_job']
+_SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions, **EMA_ABI.functions, **SAMPLER_ABI.functions,
+               **DATA_ABI.functions}
 
 _libs = {}
 _active = threading.local()

@@ -134,3 +134,100 @@ def load_checkpoint(model: Unet, opt: Optional[torch.optim.Optimizer], checkpoin
     if ema is not None:
         ema.load_state_dict(ck['ema_state_dict'])
     return model, opt, ck['epoch']
+
+
+# ----------------------------------------------------------------------------------- the epoch loop
+def train(dataloader, model: Unet, optimizer: torch.optim.Optimizer, scheduler: LinearNoiseScheduler, config: Config, *,
+          ema: Optional[EMA] = None, log=None, run_id=0) -> int:
+    """The epoch loop of ``train_ddpm.py:71-143`` over a loader of ``(B, 3, S, S)`` device batches
+    (``dataloader.get_loader``).  Per batch: ``noise = randn_like(images)``, ``t = randint(0, T, (B,))``, the
+    HIP forward with its tape (``add_noise``, the UNet), ``wc_mse_loss`` giving the loss and d loss / d pred
+    in one sweep, the HIP backward from that seed, ``optimizer.step()``, then ``ema.update()``.
+
+    ``log`` is called with the reference's two ``wandb.log`` dicts (``{'train_loss', 'epoch'}`` every
+    ``log_interval`` batches, ``{'average_epoch_loss', 'epoch'}`` per epoch); ``None`` logs nothing.  The
+    losses accumulate on the device and are read once per ``log_interval`` and once per epoch, not once per
+    iteration as ``:117-118`` do.  ``resume_training`` loads ``resume_checkpoint`` and runs ``epochs`` more
+    epochs from its epoch on, as ``:81-84`` do (the checkpoint's epoch is run again: the reference's count).
+    A checkpoint is saved every ``save_interval`` epochs under ``folders.checkpoints/<run_id>/``.  Returns
+    the last epoch run."""
+    tr = config.training
+    start_epoch, num_epochs = 1, tr.epochs
+    num_batches = len(dataloader)
+    T = config.diffusion.num_timesteps
+    if tr.resume_training:
+        model, optimizer, start_epoch = load_checkpoint(model, optimizer, tr.resume_checkpoint, ema=ema)
+        num_epochs += start_epoch  # :83
+        print(f'Resuming training from epoch {start_epoch}')
+    dev = next(model.parameters()).device
+    epoch_idx = start_epoch - 1
+    for epoch_idx in range(start_epoch, num_epochs + 1):
+        model.train()
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        interval = torch.zeros((), dtype=torch.float32, device=dev)
+        for batch_idx, images in enumerate(dataloader):
+            optimizer.zero_grad(set_to_none=True)
+            images = images.float().to(dev)
+            noise = torch.randn_like(images)
+            t = torch.randint(0, T, (images.shape[0], )).to(dev)
+            noisy = scheduler.add_noise(images, noise, t)
+            pred = model(noisy, t)
+            loss, g = K.mse_loss(pred.detach(), noise, grad=True)
+            pred.backward(g)
+            optimizer.step()
+            if ema is not None:
+                ema.update()
+            total += loss
+            interval += loss
+            if (batch_idx + 1) % tr.log_interval == 0:
+                avg = interval.item() / tr.log_interval  # the one host read of the interval
+                interval.zero_()
+                print(f'Epoch: {epoch_idx} | Batch: {batch_idx + 1}/{num_batches} | Loss: {avg:.4f}')
+                if log is not None:
+                    log({'train_loss': avg, 'epoch': epoch_idx})
+        avg_epoch = total.item() / max(num_batches, 1)
+        print(f'Finished epoch: {epoch_idx} | Average Loss: {avg_epoch:.4f}')
+        if log is not None:
+            log({'average_epoch_loss': avg_epoch, 'epoch': epoch_idx})
+        if epoch_idx % tr.save_interval == 0:
+            path = save_checkpoint(epoch_idx, model, optimizer, config.folders.checkpoints, run_id, ema=ema)
+            print(f'Saved checkpoints into {path}...')
+    print('Done Training ...')
+    return epoch_idx
+
+
+def main(config_path: Optional[str] = None, *, ema_decay: Optional[float] = 0.9999, log=None, run_id=0):
+    """``train_ddpm.py:146-199``: the loader over ACDC + BDD + DAWN, the model, Adam, the scheduler (and the
+    EMA) from the yaml, then ``train``.  ``data.image_size`` is a list in the yaml; its first entry is the
+    crop size."""
+    import random
+    from pathlib import Path
+
+    import numpy as np
+
+    from .dataloader import ACDCDataset, make_loader
+    config = load_config(config_path) if config_path else load_config()
+    seed = config.training.random_seed  # :31-34
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    random.seed(seed)
+    dev = torch.device('cuda' if config.training.device in ('auto', 'cuda') else config.training.device)
+    size = config.data.image_size
+    size = int(size[0] if isinstance(size, (list, tuple)) else size)
+    root = Path(config.data.root_dir)
+    dataset = ACDCDataset(root / config.data.acdc_images, config.data.weather, image_size=size)
+    dataset.add_images(root / config.data.bdd_dir)
+    dataset.add_images(root / config.data.dawn_dir)
+    print(len(dataset))
+    loader = make_loader(dataset, config.training.batch_size, config.training.num_workers, device=dev)
+    scheduler = LinearNoiseScheduler(config.diffusion.num_timesteps, config.diffusion.beta_start,
+                                     config.diffusion.beta_end, device=dev)
+    model = Unet(config.model).to(dev).train()
+    optimizer = make_optimizer(model, config)
+    ema = make_ema(model, ema_decay) if ema_decay is not None else None
+    return train(loader, model, optimizer, scheduler, config, ema=ema, log=log, run_id=run_id)
+
+
+if __name__ == '__main__':
+    import sys
+    main(sys.argv[1] if len(sys.argv) > 1 else None)

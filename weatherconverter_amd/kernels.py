@@ -1571,6 +1571,149 @@ def ema_swap(jobs: EmaJobs):
         _native.call('wc_ema_swap', table, n, nchunks, _stream())
 
 
+# ------------------------------------------------------------------ training input (include/wc_data.h)
+RESAMPLE_PRECISION_BITS = 22  # Pillow's PRECISION_BITS
+
+
+def resized_size(w: int, h: int, S: int) -> Tuple[int, int]:
+    """(W', H') of torchvision's Resize(S) for an int S: the smaller edge becomes S, the other
+    int(S * long / short) -- Python float division, then int()."""
+    return (S, int(S * h / w)) if w <= h else (int(S * w / h), S)
+
+
+def center_crop_origin(w: int, h: int, S: int) -> Tuple[int, int]:
+    """(left, top) of torchvision's CenterCrop(S) on a w x h image (Python's round: half to even)."""
+    return int(round((w - S) / 2.0)), int(round((h - S) / 2.0))
+
+
+@functools.lru_cache(maxsize=64)
+def resample_axis(in_size: int, out_size: int):
+    """(bounds int32 [out, 2] = (xmin, n), coefs int32 [out, ksize], ksize) of Pillow's BILINEAR resample
+    of one axis in_size -> out_size with the whole axis as the box: float64 weights (the triangle filter
+    over support = max(scale, 1), normalised by their in-order sum), then int(0.5 + w * 2^22).  Host
+    numpy only: loader workers call it."""
+    import math
+
+    import numpy as np
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)  # astype truncates, as int()
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+    n = xmax - xmin
+    x = np.arange(ksize, dtype=np.float64)[None, :]
+    a = np.abs((x + xmin[:, None] - center[:, None] + 0.5) * (1.0 / fs))
+    w = np.where(a < 1.0, 1.0 - a, 0.0)
+    w[np.arange(ksize)[None, :] >= n[:, None]] = 0.0
+    ww = np.cumsum(w, axis=1)[:, -1:]  # summed in order (the trailing zeros add nothing)
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    coefs = (0.5 + w * float(1 << RESAMPLE_PRECISION_BITS)).astype(np.int64).astype(np.int32)
+    coefs[np.arange(ksize)[None, :] >= n[:, None]] = 0
+    bounds = np.stack([xmin, n], axis=1).astype(np.int32)
+    bounds.setflags(write=False)
+    coefs.setflags(write=False)
+    return bounds, coefs, ksize
+
+
+def augment_window(w: int, h: int, S: int, crop_x: int, crop_y: int) -> Tuple[int, int, int, int]:
+    """(x, y, width, height) of the source rectangle the S x S crop window at (crop_x, crop_y) of the
+    resized image reads: the minimal upload of one image.  Host only."""
+    ow, oh = resized_size(w, h, S)
+    _req(0 <= crop_x <= ow - S and 0 <= crop_y <= oh - S, f'crop window ({crop_x}, {crop_y}) outside the {ow}x{oh} resized image')
+    hb, vb = resample_axis(w, ow)[0], resample_axis(h, oh)[0]
+    x0, y0 = int(hb[crop_x, 0]), int(vb[crop_y, 0])
+    x1, y1 = int(hb[crop_x + S - 1].sum()), int(vb[crop_y + S - 1].sum())
+    return x0, y0, x1 - x0, y1 - y0
+
+
+class AugmentGeometry(NamedTuple):
+    """The resize of one image size: (w, h) -> (out_w, out_h) for crop size S, the ksize of both axes and
+    `tables`, one int32 device tensor holding hbounds, hcoefs, vbounds, vcoefs, each 16-byte aligned, with
+    their device addresses in `pointers`."""
+    w: int
+    h: int
+    S: int
+    out_w: int
+    out_h: int
+    ksize_h: int
+    ksize_v: int
+    tables: torch.Tensor
+    pointers: Tuple[int, int, int, int]  # hbounds, hcoefs, vbounds, vcoefs
+
+
+_AUGMENT_GEOMETRIES: Dict[tuple, AugmentGeometry] = {}
+
+
+def _check_axis_against_native(in_size: int, out_size: int, bounds) -> None:
+    """wc_augment_batch sizes its launch from the bounds arithmetic evaluated in C (wc_resample_span) while the
+    kernel walks these numpy-made tables: refuse tables the two do not agree on, index by index."""
+    lib = _native.load()
+    first, count = ctypes.c_int64(), ctypes.c_int64()
+    for o in range(out_size):
+        _native.check(lib.wc_resample_span(in_size, out_size, o, o + 1, ctypes.byref(first), ctypes.byref(count)),
+                      'wc_resample_span')
+        _req(first.value == int(bounds[o, 0]) and count.value == int(bounds[o, 1]),
+             f'resample tables of axis {in_size} -> {out_size} differ from the native bounds at index {o}')
+
+
+def augment_geometry(w: int, h: int, S: int, device) -> AugmentGeometry:
+    """The device coefficient tables of geometry (w, h, S), made once per device and kept: a dataset has a
+    handful of image sizes.  Uploaded with a blocking copy, so every stream may read them afterwards."""
+    device = torch.device(device)
+    key = (w, h, S, device.type, torch.cuda.current_device() if device.index is None else device.index)
+    g = _AUGMENT_GEOMETRIES.get(key)
+    if g is None:
+        _req(min(w, h) >= 1 and S >= 1, f'augment geometry: a {w}x{h} image to {S}')
+        ow, oh = resized_size(w, h, S)
+        hb, hc, kh = resample_axis(w, ow)
+        vb, vc, kv = resample_axis(h, oh)
+        _check_axis_against_native(w, ow, hb)
+        _check_axis_against_native(h, oh, vb)
+        parts = [torch.from_numpy(a.copy()).reshape(-1) for a in (hb, hc, vb, vc)]
+        offs = [0]
+        for p in parts:
+            offs.append(offs[-1] + -(-p.numel() // 4) * 4)  # every table 16-byte aligned
+        flat = torch.zeros(offs[-1], dtype=torch.int32)
+        for o, p in zip(offs, parts):
+            flat[o:o + p.numel()] = p
+        tables = flat.to(device)
+        g = AugmentGeometry(w, h, S, ow, oh, kh, kv, tables, tuple(tables.data_ptr() + 4 * o for o in offs[:4]))
+        _AUGMENT_GEOMETRIES[key] = g
+    return g
+
+
+AUGMENT_JOB_WORDS = ctypes.sizeof(_native.AugmentJob) // 8
+
+
+def augment_job_words(geom: AugmentGeometry, src_ptr: int, pitch: int, rect: Tuple[int, int, int, int], crop_x: int,
+                      crop_y: int, flip: bool) -> List[int]:
+    """One wc_augment_job as its int64 words, in the header's field order."""
+    return [src_ptr, pitch, rect[0], rect[1], rect[2], rect[3], geom.w, geom.h, geom.out_w, geom.out_h,
+            *geom.pointers, geom.ksize_h, geom.ksize_v, crop_x, crop_y, int(bool(flip))]
+
+
+def augment_batch(host_jobs: torch.Tensor, dev_jobs: torch.Tensor, S: int, out: torch.Tensor) -> torch.Tensor:
+    """out[B, 3, S, S] = Resize(S) -> crop -> flip -> ToTensor -> x * 2 - 1 of every job, ONE launch on the
+    current stream (wc_augment_batch).  host_jobs: int64 [B, AUGMENT_JOB_WORDS] on the host, dev_jobs: the
+    same rows on out's device (the caller orders their upload before this call on the same stream)."""
+    B = host_jobs.shape[0]
+    _req(host_jobs.dtype == torch.int64 and not host_jobs.is_cuda and host_jobs.is_contiguous()
+         and host_jobs.dim() == 2 and host_jobs.shape[1] == AUGMENT_JOB_WORDS and B >= 1,
+         f'augment_batch: host jobs are int64 [B, {AUGMENT_JOB_WORDS}] rows')
+    _req(dev_jobs.is_cuda and dev_jobs.device == out.device and dev_jobs.is_contiguous()
+         and dev_jobs.numel() * dev_jobs.element_size() >= 8 * B * AUGMENT_JOB_WORDS and dev_jobs.data_ptr() % 8 == 0,
+         'augment_batch: device jobs are the same rows on the output device')
+    _req(out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 3, S, S),
+         f'augment_batch: out is a contiguous fp32 ({B}, 3, {S}, {S}) device tensor')
+    J = ctypes.POINTER(_native.AugmentJob)
+    with torch.cuda.device(out.device):
+        _native.call('wc_augment_batch', ctypes.cast(host_jobs.data_ptr(), J), ctypes.cast(dev_jobs.data_ptr(), J), B, S,
+                     out.data_ptr(), _stream())
+    return out
+
+
 def philox_normal(shape, device, seed: int, sample0: int = 0, step: int = 0) -> torch.Tensor:
     out = torch.empty(shape, dtype=torch.float32, device=device)
     B = shape[0]

@@ -20,6 +20,7 @@ from typing import Optional
 
 import torch
 
+from .diffusion_model.dataloader import load_image  # noqa: F401  (translation.py:131-143: the input of sample_with_sgg)
 from .sgg.sgg import apply_gsg, apply_lcg
 from .srgan_model.models import inference as srgan_inference
 
