@@ -14,6 +14,7 @@
 #include "wc_kernels.h"
 #include "wc_optim.h"
 #include "wc_sampler.h"
+#include "wc_seg.h"
 
 #include "conv_args_mutations.hpp"
 
@@ -192,6 +193,72 @@ int main() {
         EXPECT(wc_resample_span(40, 85, 10, 10, &first, &count), WC_E_SHAPE);
         EXPECT(wc_resample_span(40, 85, 0, 86, &first, &count), WC_E_SHAPE);
         EXPECT(wc_resample_span(40, 85, 0, 85, nullptr, &count), WC_E_ARG);
+    }
+
+    // Segmentation labels and metrics (include/wc_seg.h): every check runs before any launch.
+    {
+        alignas(16) static unsigned char lut[256];
+        std::vector<int> rows(6), cols(5);
+        for (int i = 0; i < 6; ++i) rows[i] = i;
+        for (int i = 0; i < 5; ++i) cols[i] = i;
+        wc_label_job good;
+        std::memset(&good, 0, sizeof(good));
+        good.src = p;
+        good.pitch = 5;
+        good.rect_w = 5;
+        good.rect_h = 6;
+        good.rows = good.cols = (const int*)p;  // device tables: never read on the host
+        good.rows_host = rows.data();
+        good.cols_host = cols.data();
+        float* a16 = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15));
+        int64_t* out64 = (int64_t*)a16;
+        EXPECT(wc_label_batch(nullptr, &good, 1, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        EXPECT(wc_label_batch(&good, nullptr, 1, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        EXPECT(wc_label_batch(&good, &good, 1, 6, 5, nullptr, out64, nullptr), WC_E_SHAPE);
+        EXPECT(wc_label_batch(&good, &good, 1, 6, 5, lut, nullptr, nullptr), WC_E_SHAPE);
+        EXPECT(wc_label_batch(&good, &good, 0, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        EXPECT(wc_label_batch(&good, &good, 65536, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        EXPECT(wc_label_batch(&good, &good, 1, 0, 5, lut, out64, nullptr), WC_E_SHAPE);
+        EXPECT(wc_label_batch(&good, &good, 1, 6, 0, lut, out64, nullptr), WC_E_SHAPE);
+        wc_label_job j = good;
+        j.pitch = 4;
+        EXPECT(wc_label_batch(&j, &good, 1, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        j = good;
+        j.rows_host = nullptr;
+        EXPECT(wc_label_batch(&j, &good, 1, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        rows[5] = 6;  // the last row entry outside the rectangle: the whole table is walked, and no further
+        EXPECT(wc_label_batch(&good, &good, 1, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        rows[5] = 5;
+        cols[4] = -1;
+        EXPECT(wc_label_batch(&good, &good, 1, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+        cols[4] = 4;
+        wc_label_job two[2] = {good, good};
+        two[1].rect_h = 5;  // row entry 5 is outside the second job's rectangle
+        EXPECT(wc_label_batch(two, two, 2, 6, 5, lut, out64, nullptr), WC_E_SHAPE);
+
+        const float* lg = a16;
+        const int64_t* lb = (const int64_t*)a16;
+        EXPECT(wc_seg_confusion(nullptr, lb, 1, 19, 8, 8, out64, nullptr, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_confusion(lg, nullptr, 1, 19, 8, 8, out64, nullptr, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_confusion(lg, lb, 1, 19, 8, 8, nullptr, nullptr, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_confusion(lg + 1, lb, 1, 19, 8, 8, out64, nullptr, nullptr), WC_E_ARG);  // misaligned logits
+        EXPECT(wc_seg_confusion(lg, lb, 1, 1, 8, 8, out64, nullptr, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_confusion(lg, lb, 1, 33, 8, 8, out64, nullptr, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_confusion(lg, lb, 0, 19, 8, 8, out64, nullptr, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_confusion(lg, lb, 1, 19, 0, 8, out64, nullptr, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_confusion(lg, lb, 1 << 20, 19, 1 << 11, 1 << 11, out64, nullptr, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_confusion_pred(nullptr, lb, 1, 19, 8, 8, out64, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_confusion_pred(p, lb, 1, 33, 8, 8, out64, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_confusion_pred(p, lb, 1, 19, 8, 0, out64, nullptr), WC_E_SHAPE);
+        unsigned char palette[20 * 3] = {0};
+        EXPECT(wc_seg_decode(nullptr, 0, 64, 19, palette, p, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_decode(p, 0, 64, 19, nullptr, p, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_decode(p, 0, 64, 19, palette, nullptr, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_decode(p, 2, 64, 19, palette, p, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_decode((const char*)a16 + 4, 1, 64, 19, palette, p, nullptr), WC_E_ARG);
+        EXPECT(wc_seg_decode(p, 0, 0, 19, palette, p, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_decode(p, 0, 64, 1, palette, p, nullptr), WC_E_SHAPE);
+        EXPECT(wc_seg_decode(p, 0, 64, 33, palette, p, nullptr), WC_E_SHAPE);
     }
 
     // Round-3 training entry points: weight gradients, split-precision attention backward, bounds.

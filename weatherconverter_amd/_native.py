@@ -38,8 +38,12 @@ SAMPLER_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_sampler.h'
 # And the training-input kernel (wc_augment_batch: Pillow-exact resize, crop, flip and normalisation).
 DATA_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_data.h')).read())
 AugmentJob = DATA_ABI.structs['wc_augment_job']
+# And the segmentation label and metric kernels (wc_label_batch, wc_seg_confusion, wc_seg_confusion_pred,
+# wc_seg_decode).
+SEG_ABI = _abi.read(open(os.path.join(_build.ROOT, 'include', 'wc_seg.h')).read())
+LabelJob = SEG_ABI.structs['wc_label_job']
 _SIGNATURES = {**ABI.functions, **OPTIM_ABI.functions, **EMA_ABI.functions, **SAMPLER_ABI.functions,
-               **DATA_ABI.functions}
+               **DATA_ABI.functions, **SEG_ABI.functions}
 
 _libs = {}
 _active = threading.local()

@@ -1714,6 +1714,110 @@ def augment_batch(host_jobs: torch.Tensor, dev_jobs: torch.Tensor, S: int, out: 
     return out
 
 
+# ------------------------------------------------------------------ segmentation labels and metrics (include/wc_seg.h)
+SEG_MAX_CLASSES = 32
+
+
+@functools.lru_cache(maxsize=64)
+def nearest_table(in_size: int, out_size: int):
+    """int32 [out_size]: the source index of every output index of Pillow's NEAREST resize of one axis
+    in_size -> out_size.  Pillow runs a scale-only affine map and ACCUMULATES the source coordinate in
+    double: a = in / out; xo = a * 0.5; per output index, in order: idx = int(xo); xo += a.  The table repeats
+    that arithmetic step by step (a 16.16 fixed-point walk of the same map differs from Pillow for some size
+    pairs).  Host numpy only."""
+    import numpy as np
+    _req(in_size >= 1 and out_size >= 1, f'nearest_table: axis {in_size} -> {out_size}')
+    a = float(in_size) / float(out_size)
+    xo = a * 0.5
+    idx = np.empty(out_size, dtype=np.int32)
+    for o in range(out_size):
+        idx[o] = int(xo)
+        xo += a
+    assert int(idx.min()) >= 0 and int(idx.max()) < in_size, (in_size, out_size)
+    idx.setflags(write=False)
+    return idx
+
+
+LABEL_JOB_WORDS = ctypes.sizeof(_native.LabelJob) // 8
+
+
+def label_job_words(src_ptr: int, pitch: int, rect_w: int, rect_h: int, rows_ptr: int, cols_ptr: int, rows_host_ptr: int,
+                    cols_host_ptr: int) -> List[int]:
+    """One wc_label_job as its int64 words, in the header's field order."""
+    return [src_ptr, pitch, rect_w, rect_h, rows_ptr, cols_ptr, rows_host_ptr, cols_host_ptr]
+
+
+def label_batch(host_jobs: torch.Tensor, dev_jobs: torch.Tensor, lut: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[b, y, x] = lut[src_b[rows_b[y], cols_b[x]]] (int64 [B, Hc, Wc]) for every job, ONE launch on the
+    current stream (wc_label_batch).  host_jobs: int64 [B, LABEL_JOB_WORDS] on the host (its rows_host /
+    cols_host words point at host int32 tables the caller keeps alive over this call), dev_jobs: the same rows
+    on out's device, lut: 256 uint8 on the host."""
+    B = host_jobs.shape[0]
+    _req(host_jobs.dtype == torch.int64 and not host_jobs.is_cuda and host_jobs.is_contiguous()
+         and host_jobs.dim() == 2 and host_jobs.shape[1] == LABEL_JOB_WORDS and B >= 1,
+         f'label_batch: host jobs are int64 [B, {LABEL_JOB_WORDS}] rows')
+    _req(dev_jobs.is_cuda and dev_jobs.device == out.device and dev_jobs.is_contiguous()
+         and dev_jobs.numel() * dev_jobs.element_size() >= 8 * B * LABEL_JOB_WORDS and dev_jobs.data_ptr() % 8 == 0,
+         'label_batch: device jobs are the same rows on the output device')
+    _req(lut.dtype == torch.uint8 and not lut.is_cuda and lut.is_contiguous() and lut.numel() == 256,
+         'label_batch: lut is 256 uint8 on the host')
+    _req(out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.dim() == 3 and out.shape[0] == B,
+         f'label_batch: out is a contiguous int64 ({B}, Hc, Wc) device tensor')
+    J = ctypes.POINTER(_native.LabelJob)
+    with torch.cuda.device(out.device):
+        _native.call('wc_label_batch', ctypes.cast(host_jobs.data_ptr(), J), ctypes.cast(dev_jobs.data_ptr(), J), B,
+                     out.shape[1], out.shape[2], lut.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
+def seg_confusion(scores: torch.Tensor, labels: torch.Tensor, hist: torch.Tensor,
+                  pred: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hist[label, pred] += 1 over every pixel with 0 <= label < C, on the current stream, no host sync.
+    scores: fp32 logits (B, C, H, W) -- the argmax (numpy's: first maximum, first NaN) is fused, and `pred`
+    (uint8 (B, H, W)) receives it when given (wc_seg_confusion) -- or a ready uint8 prediction map (B, H, W)
+    (wc_seg_confusion_pred; a prediction >= C is ignored like a bad label).  labels: int64 (B, H, W);
+    hist: int64 (C, C), added to."""
+    _req(hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.dim() == 2
+         and hist.shape[0] == hist.shape[1], 'seg_confusion: hist is a contiguous int64 (C, C) device tensor')
+    C = hist.shape[0]
+    fused = scores.dtype == torch.float32
+    _req(scores.is_cuda and scores.device == hist.device and scores.is_contiguous()
+         and (scores.dim() == 4 and scores.shape[1] == C if fused else scores.dtype == torch.uint8 and scores.dim() == 3),
+         f'seg_confusion: scores are contiguous fp32 (B, {C}, H, W) logits or a uint8 (B, H, W) map on hist\'s device')
+    B, (H, W) = scores.shape[0], scores.shape[-2:]
+    _req(labels.is_cuda and labels.device == hist.device and labels.dtype == torch.int64 and labels.is_contiguous()
+         and tuple(labels.shape) == (B, H, W), f'seg_confusion: labels are a contiguous int64 ({B}, {H}, {W}) device tensor')
+    _req(not fused or scores.data_ptr() % 16 == 0, 'seg_confusion: logits must be 16-byte aligned')
+    _req(pred is None or (fused and pred.is_cuda and pred.device == hist.device and pred.dtype == torch.uint8
+                          and pred.is_contiguous() and tuple(pred.shape) == (B, H, W)),
+         f'seg_confusion: pred is a contiguous uint8 ({B}, {H}, {W}) device tensor, with logits only')
+    with torch.cuda.device(hist.device):
+        if fused:
+            _native.call('wc_seg_confusion', scores.data_ptr(), labels.data_ptr(), B, C, H, W, hist.data_ptr(),
+                         _ptr(pred), _stream())
+        else:
+            _native.call('wc_seg_confusion_pred', scores.data_ptr(), labels.data_ptr(), B, C, H, W, hist.data_ptr(),
+                         _stream())
+    return hist
+
+
+def seg_decode(class_map: torch.Tensor, palette: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 (*class_map.shape, 3) colours of a uint8 or int64 device class map through `palette` (uint8
+    (C + 1, 3) on the host); every value >= C or negative takes the last colour.  class_map is only read."""
+    _req(class_map.is_cuda and class_map.dtype in (torch.uint8, torch.int64) and class_map.is_contiguous()
+         and class_map.numel() >= 1, 'seg_decode: the map is a contiguous uint8 or int64 device tensor')
+    _req(palette.dtype == torch.uint8 and not palette.is_cuda and palette.is_contiguous() and palette.dim() == 2
+         and palette.shape[1] == 3, 'seg_decode: palette is uint8 (C + 1, 3) on the host')
+    if out is None:
+        out = torch.empty(tuple(class_map.shape) + (3, ), dtype=torch.uint8, device=class_map.device)
+    _req(out.is_cuda and out.device == class_map.device and out.dtype == torch.uint8 and out.is_contiguous()
+         and tuple(out.shape) == tuple(class_map.shape) + (3, ), 'seg_decode: out is uint8 (*map.shape, 3) on the map\'s device')
+    with torch.cuda.device(out.device):
+        _native.call('wc_seg_decode', class_map.data_ptr(), int(class_map.dtype == torch.int64), class_map.numel(),
+                     palette.shape[0] - 1, palette.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
 def philox_normal(shape, device, seed: int, sample0: int = 0, step: int = 0) -> torch.Tensor:
     out = torch.empty(shape, dtype=torch.float32, device=device)
     B = shape[0]

@@ -7,7 +7,7 @@ SURVEY §8(f) #3), and it differentiates a detached copy instead of flipping ``r
 caller's tensor (reference :132).  The pooled-gradient magnitude runs in the ``wc_sgg_update`` HIP
 kernel instead of the reference's host numpy round trip (:36-53).
 """
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -48,6 +48,38 @@ def infer(model: torch.nn.Module, input_tensor: torch.Tensor, encoded_label_tens
     if verbose:
         print(f'output {tuple(out.shape)}, grad {tuple(g.shape)}')
     return pred, g, g.detach().cpu().squeeze(0).numpy()
+
+
+@torch.no_grad()
+def predict(model: torch.nn.Module, x: torch.Tensor, *, metrics=None, gt: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 (B, H, W) device prediction of ``model(x)``: the argmax runs fused in ``wc_seg_confusion`` and
+    nothing is copied to the host (the reference's ``infer`` returns ``argmax(1).cpu().numpy()``).  With
+    ``metrics`` (a ``StreamSegMetrics`` of the model's class count) and ``gt`` (int64 (B, H, W) or
+    (B, 1, H, W) train ids) the same launch adds the batch to the metric; without them the labels are all
+    ignored and only the prediction is written."""
+    from .metrics import StreamSegMetrics
+    out = model(x).float().contiguous()
+    B, C, H, W = out.shape
+    pred = torch.empty((B, H, W), dtype=torch.uint8, device=out.device)
+    if (metrics is None) != (gt is None):
+        raise ValueError('predict: metrics and gt go together')
+    if metrics is None:
+        metrics = StreamSegMetrics(C, out.device)
+        gt = torch.full((B, H, W), 255, dtype=torch.int64, device=out.device)
+    elif metrics.n_classes != C:
+        raise ValueError(f'predict: the metric counts {metrics.n_classes} classes, the model predicts {C}')
+    metrics.update(gt.reshape(B, H, W), out, pred_out=pred)
+    return pred
+
+
+def semantic_score(model: torch.nn.Module, x: torch.Tensor, gt: torch.Tensor, n_classes: int = 19) -> dict:
+    """``StreamSegMetrics(n_classes).get_results()`` of ``model(x)`` against ``gt`` for one batch (the scoring
+    of reference ``seg_model/train.py:263-279``): Overall Acc, Mean Acc, FreqW Acc, Mean IoU, Class IoU.  The
+    counts are made on the device; reading them is the one host synchronisation."""
+    from .metrics import StreamSegMetrics
+    metrics = StreamSegMetrics(n_classes, x.device)
+    predict(model, x, metrics=metrics, gt=gt)
+    return metrics.get_results()
 
 
 def compute_gradient_magnitude(input_gradients: torch.Tensor, denormalize: bool = True, norm: bool = False) -> torch.Tensor:

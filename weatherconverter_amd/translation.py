@@ -15,6 +15,11 @@ reproduced: the last step returns ``mu`` as ``sample_ddpm`` does.  LCG runs only
 ``steps=`` walks a sub-sequence tau of [0, N) instead (``timestep_sequence`` with N in place of T), with
 (mu, sigma*z) from ``scheduler.ddim_prev_timestep``; GSG runs where the position k of tau is odd and LCG
 on even k, which at stride 1 is the parity of i above.
+
+``translate_files`` drives the loop from files (``load_image`` for the frame, ``seg_model.datasets.label_for``
+for its labelIds map) and scores the result with the segmenter the guidance used; ``python -m
+weatherconverter_amd.translation`` is the reference's ``__main__`` (``translation.py:100-162``) with its
+hard-coded paths as arguments.
 """
 from typing import Optional
 
@@ -103,3 +108,77 @@ def sample_with_sgg(input_tensor: torch.Tensor, diff_model, diff_scheduler, seg_
             progress(i)
     sr_x0 = srgan_inference(srgan_model, xt)  # translation.py:95
     return (sr_x0, xt) if return_latent else sr_x0
+
+
+def srgan_scale(srgan_model) -> int:
+    """The generator's upscale factor: one x2 PixelShuffle block per ``upsampler`` entry."""
+    return 2 ** len(srgan_model.upsampler)
+
+
+def _num_classes(seg_model) -> int:
+    return seg_model.classifier.classifier[-1].out_channels
+
+
+def translate_files(image_path, label_path, diff_model, diff_scheduler, seg_model, srgan_model, *,
+                    image_size: Optional[int] = None, **sample_kwargs) -> dict:
+    """One guided translation from files.  The frame goes through ``load_image(image_path, image_size)``
+    (``image_size`` defaults to the UNet's ``im_size``), the labelIds file through ``label_for`` at the SRGAN
+    factor, so both show the same field of view; ``sample_with_sgg(**sample_kwargs)`` translates, and the
+    segmenter the guidance used scores the output against the label.  Returns ``{'output': (1, 3, S, S) fp32,
+    'pred': uint8 (1, S, S) prediction on the output, 'score': the StreamSegMetrics results dict}``; everything
+    stays on the device until the score's counts are read."""
+    from .seg_model.datasets import label_for
+    from .seg_model.inference import predict
+    from .seg_model.metrics import StreamSegMetrics
+    if sample_kwargs.get('return_latent'):
+        raise ValueError('translate_files returns the super-resolved output only')
+    dev = diff_scheduler.device
+    S = int(image_size if image_size is not None else diff_model.model_config.im_size)
+    x = load_image(image_path, S, dev)
+    gt = label_for(label_path, S, scale=srgan_scale(srgan_model), device=dev)
+    output = sample_with_sgg(x, diff_model, diff_scheduler, seg_model, gt, srgan_model, **sample_kwargs)
+    metrics = StreamSegMetrics(_num_classes(seg_model), dev)
+    pred = predict(seg_model, output, metrics=metrics, gt=gt)
+    return {'output': output, 'pred': pred, 'score': metrics.get_results()}
+
+
+def main(argv=None) -> dict:
+    """The reference's ``__main__`` with its paths as arguments: translate --image guided by --labels, write
+    ``output.png`` and the colourised prediction ``pred_color.png`` under --out, print the score."""
+    import argparse
+    import os
+
+    from .diffusion_model import sample_ddpm as ddpm
+    from .seg_model import inference as seg_infer
+    from .seg_model.datasets import decode_target
+    from .seg_model.metrics import StreamSegMetrics
+    from .srgan_model import models as srgan
+    ap = argparse.ArgumentParser(prog='weatherconverter_amd.translation', description=main.__doc__)
+    ap.add_argument('--image', required=True, help='the frame (RGB image file)')
+    ap.add_argument('--labels', required=True, help='its Cityscapes labelIds PNG (mode L)')
+    ap.add_argument('--diff-config', required=True, help="the diffusion model's config.yaml")
+    ap.add_argument('--diff-ckpt', required=True)
+    ap.add_argument('--seg-ckpt', required=True)
+    ap.add_argument('--srgan-ckpt', required=True)
+    ap.add_argument('--out', required=True, help='output directory')
+    ap.add_argument('--steps', type=int, default=None, help='strided sampling over this many of the N timesteps')
+    ap.add_argument('--mode', choices=('applied', 'reference'), default='applied')
+    ap.add_argument('--N', type=int, default=500, help='timesteps of the guided loop (reference: 500)')
+    ap.add_argument('--LAMBDA', type=float, default=60.0, help='guidance weight (reference: 60)')
+    args = ap.parse_args(argv)
+    config = ddpm.load_config(args.diff_config)
+    diff_model = ddpm.load_model(args.diff_ckpt, config.model)
+    diff_scheduler = ddpm.load_scheduler(config.diffusion)
+    srgan_model = srgan.load_model(args.srgan_ckpt)
+    seg_model = seg_infer.load_model(args.seg_ckpt)
+    res = translate_files(args.image, args.labels, diff_model, diff_scheduler, seg_model, srgan_model,
+                          image_size=config.model.im_size, steps=args.steps, mode=args.mode, N=args.N, LAMBDA=args.LAMBDA)
+    os.makedirs(args.out, exist_ok=True)
+    ddpm.save_png(res['output'][0].clamp(0, 1), os.path.join(args.out, 'output.png'))
+    ddpm.save_png(decode_target(res['pred'])[0].permute(2, 0, 1), os.path.join(args.out, 'pred_color.png'))
+    print(StreamSegMetrics.to_str(res['score']))
+    return res
+
+
+if __name__ == '__main__':
+    main()
